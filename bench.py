@@ -16,6 +16,8 @@ Also reported on the same JSON line:
                  Sponza-class 262 144 PLOC++ + the BVH4 collapse (config 4), uniform 2 M HPLOC (config 5's per-GPU mesh), each with the FIRST build of that size on a
                  fresh context beside the warm loop (the library sizes some launch batches from the previous same-size build);
   config5      — (N > 1) the same exchange with config 5's own shape: 2 M triangles per GPU, seed 100 + rank, offset (rank, 0, 0).
+--dump-outputs DIR writes rank 0's last timed build (sort, leaves, numbering-independent node rows; a fixed sample at large sizes) as .npy files:
+the meshes are seeded, so two builds of the project run with the same arguments can be compared output for output (dump_outputs).
 Algorithmic bytes of the PLOC-family emit stages are exact per mesh: profiles/algorithmic_bytes.json, written by
 tools/algorithmic_bytes.py from the pinned oracle's cluster-load / store counts; the split of the HPLOC emit between its two kernels is the
 measured task share of profiles/hploc_task_share.json (tools/measure_task_share.py).  Both are data files: nothing here calls the oracle outside
@@ -177,6 +179,65 @@ def kernel_bytes_per_prim(name: str, algo: str, workload: str):
     return KERNEL_BYTES_PER_PRIM.get(f"{algo}:{name}", KERNEL_BYTES_PER_PRIM.get(name, 0.0)), "SURVEY.md 8(d) constant"
 
 
+DUMP_ROWS = 1 << 18          # rows per dumped array: a fixed, seeded sample of larger outputs (~38 MB in all at 10 M triangles)
+DUMP_SEED = 12345
+
+
+def _sample_rows(count: int, rows: int | None = None) -> np.ndarray:
+    """Ascending positions of a fixed sample of `rows` (DUMP_ROWS) out of `count` (all of them when count <= rows): the same for every run of the same size."""
+    rows = DUMP_ROWS if rows is None else rows
+    if count <= rows:
+        return np.arange(count)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(count, rows, replace=False))
+
+
+def dump_outputs(res: dict, out_dir: str) -> dict:
+    """Writes a build's result (the dict of _Builder.download()) as float32 / float64 .npy files under out_dir, so that two builds of the
+    project can be compared output for output.  u32 values are exact in float64, boxes keep their float32 bits.
+
+      sorted_keys    [k] (u64 keys: [k, 2] high / low words) and sorted_vals [k]: the sort stage, at fixed sampled positions
+      leaves         [k, 7]: primitive index, box min xyz, box max xyz of the leaves in Morton order (PrimRef[n], or nodes n-1.. of the LBVH layout)
+      internal_nodes [k, 18]: box of an internal node, box of its left child, box of its right child.  HPLOC / PLOC++ number their nodes
+                     in completion order, which varies from run to run, so the rows are ordered by a hash of their contents before the
+                     sample is taken: the same tree gives the same file whatever its numbering (child order stays significant).
+      root_aabb, scene [6]; meta [4]: n_leaves, n_internal, layout, key bits
+    Returns {name: array} of what was written."""
+    nodes = np.ascontiguousarray(res["nodes"]).view(np.uint32).reshape(-1, 8)       # Bvh2Node: left, right, min xyz, max xyz
+    keys, vals = res["sorted_keys"], res["sorted_vals"]
+    n = len(vals); ni = n - 1
+    if res["layout"] == 1:
+        lw = np.ascontiguousarray(res["leaves"]).view(np.uint32).reshape(-1, 7)      # PrimRef: prim, min xyz, max xyz
+        boxes = np.concatenate([nodes[:ni, 2:8], lw[:, 1:7]])
+        leaf_prim, leaf_box = lw[:, 0], lw[:, 1:7]
+    else:
+        boxes = nodes[:, 2:8]
+        leaf_prim, leaf_box = nodes[ni:, 0], nodes[ni:, 2:8]
+    boxes = np.concatenate([boxes, np.full((1, 6), 0xFFFFFFFF, np.uint32)])          # child indices out of range read this row
+    lc = np.minimum(nodes[:ni, 0], len(boxes) - 1); rc = np.minimum(nodes[:ni, 1], len(boxes) - 1)
+
+    def words(j):          # column j of the canonical row of every internal node
+        return nodes[:ni, 2 + j] if j < 6 else boxes[lc if j < 12 else rc, j % 6]
+    h = np.full(ni, 0xCBF29CE484222325, np.uint64)                                   # FNV-1a over the 18 words
+    for j in range(18):
+        h = (h ^ words(j).astype(np.uint64)) * np.uint64(0x100000001B3)
+    pick = np.argsort(h, kind="stable")[_sample_rows(ni)]
+    internal = np.stack([nodes[pick, 2 + j] if j < 6 else boxes[(lc if j < 12 else rc)[pick], j % 6] for j in range(18)], axis=1)
+
+    s = _sample_rows(n)
+    k = keys[s]
+    out = {"sorted_keys": (np.stack([k >> np.uint64(32), k & np.uint64(0xFFFFFFFF)], axis=1) if k.dtype == np.uint64 else k).astype(np.float64),
+           "sorted_vals": vals[s].astype(np.float64),
+           "leaves": np.concatenate([leaf_prim[s, None].astype(np.float64), leaf_box[s].view(np.float32).astype(np.float64)], axis=1),
+           "internal_nodes": np.ascontiguousarray(internal).view(np.float32),
+           "root_aabb": (boxes[res["root"]] if ni > 0 else leaf_box[0]).view(np.float32).copy(),
+           "scene": np.ascontiguousarray(res["scene"]).view(np.float32).reshape(6).copy(),
+           "meta": np.array([n, ni, res["layout"], 64 if keys.dtype == np.uint64 else 32], np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -188,7 +249,10 @@ def main() -> None:
     ap.add_argument("--cpu-sample", type=int, default=10_000_000, help="triangles of the mesh the CPU baseline is timed on (0 = skip); the whole 10 M mesh is ~25 s of single-thread work")
     ap.add_argument("--no-kernel-events", action="store_true", help="do not bracket kernels with HIP events in the timed region")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false", help="skip the other configs' loops (N = 1) / the config-5-shaped exchange (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the result of the last timed build as .npy files to DIR (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import bvh_pkg
@@ -296,6 +360,8 @@ def main() -> None:
     if gather and backend == "nccl":      # every rank holds every root box, and this rank's slot is its own tree's root
         torch.cuda.synchronize()
         assert torch.equal(gathered[6 * rank: 6 * rank + 6], root_box), "all-gather of root AABBs is inconsistent"
+    if args.dump_outputs and rank == 0:                      # the last timed build's result, before the extra build below replaces it
+        dump_outputs(builder.download(), args.dump_outputs)
     ctx.set_kernel_sampling(1); ctx.set_profiling(1)
     builder.build(ctx, d_tris, on_device=True, n=n)          # one extra build with stage events (reference Timer tokens)
     stage = dict(builder.m_timer)

@@ -4,6 +4,7 @@ import importlib.util
 import json
 import os
 
+import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
@@ -49,3 +50,64 @@ def test_issue_counter_file_is_recomputable():
     valu = e["SQ_INSTS_VALU"] * e["cycles_per_valu_inst"] / (e["simds"] * cyc)
     lds = e["SQ_INSTS_LDS"] * e["cycles_per_lds_inst"] / (e["cus"] * cyc)
     assert 0.3 < valu <= 1.0 and 0.3 < lds < 1.0 and 0.3 < e["SQ_WAIT_ANY"] / e["SQ_WAVE_CYCLES"] < 0.8
+
+
+def _as_result(ref):
+    return {"nodes": ref["nodes"], "leaves": ref["leaves"], "sorted_keys": ref["skeys"], "sorted_vals": ref["svals"], "scene": ref["scene"],
+            "root": ref["root"], "layout": ref["layout"]}
+
+
+def _renumbered(res, seed):
+    """the same tree with its internal nodes stored in another order (as HPLOC / PLOC++ may number them from run to run)"""
+    nodes = res["nodes"]
+    ni = len(res["sorted_vals"]) - 1
+    perm = np.random.default_rng(seed).permutation(ni)                 # new position of old node i
+    out = nodes.copy()
+    out[perm] = nodes[:ni]
+    for f in ("left", "right"):
+        c = out[f][:ni]
+        out[f][:ni] = np.where(c < ni, perm[np.minimum(c, ni - 1)], c)
+    return dict(res, nodes=out, root=int(perm[res["root"]]))
+
+
+@pytest.mark.parametrize("algo", [1, 3])
+def test_dump_outputs_is_numbering_independent(pkg, orc, tmp_path, algo):
+    """bench.py --dump-outputs: float32 / float64 files only, the whole result at this size, the same files for a renumbered tree and
+    different ones for a tree with two children swapped"""
+    b = _bench()
+    tris = pkg.meshgen.uniform(5000, 7)
+    n = len(tris)
+    res = _as_result(orc.build_tree(algo, tris))
+    got = b.dump_outputs(res, str(tmp_path / "a"))
+    assert set(got) == {"sorted_keys", "sorted_vals", "leaves", "internal_nodes", "root_aabb", "scene", "meta"}
+    for name, a in got.items():
+        back = np.load(tmp_path / "a" / (name + ".npy"))
+        assert back.dtype in (np.float32, np.float64) and np.array_equal(back, a, equal_nan=True)
+    assert np.array_equal(got["sorted_keys"], res["sorted_keys"].astype(np.float64)) and np.array_equal(got["leaves"][:, 0], res["sorted_vals"].astype(np.float64))
+    assert got["internal_nodes"].shape == (n - 1, 18) and got["leaves"].shape == (n, 7)
+    nd = res["nodes"][res["root"]]
+    assert np.array_equal(got["root_aabb"], np.concatenate([nd["min"], nd["max"]]))
+    assert list(got["meta"]) == [n, n - 1, res["layout"], 32]
+
+    again = b.dump_outputs(_renumbered(res, 1), str(tmp_path / "b"))
+    assert all(np.array_equal(got[k], again[k]) for k in got)
+
+    swapped = dict(res, nodes=res["nodes"].copy())
+    swapped["nodes"]["left"][res["root"]], swapped["nodes"]["right"][res["root"]] = res["nodes"]["right"][res["root"]], res["nodes"]["left"][res["root"]]
+    assert not np.array_equal(b.dump_outputs(swapped, str(tmp_path / "c"))["internal_nodes"], got["internal_nodes"])
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(pkg, orc, tmp_path, monkeypatch):
+    """larger outputs are cut to a fixed, seeded sample of rows: the same rows every run, at most 64 MB at the benchmark's 10 M triangles"""
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_ROWS", 256)
+    res = _as_result(orc.build_tree(3, pkg.meshgen.uniform(4000, 3)))
+    one = b.dump_outputs(res, str(tmp_path / "a"))
+    two = b.dump_outputs(_renumbered(res, 2), str(tmp_path / "b"))
+    assert all(np.array_equal(one[k], two[k]) for k in one)
+    assert one["internal_nodes"].shape == (256, 18) and one["leaves"].shape == (256, 7) and one["sorted_keys"].shape == (256,)
+    assert np.all(np.diff(one["sorted_keys"]) >= 0)
+    s = b._sample_rows(4000, 256)
+    assert np.array_equal(one["sorted_vals"], res["sorted_vals"][s].astype(np.float64))
+    k = _bench().DUMP_ROWS                  # at the benchmark's size (10 M triangles, u32 keys): keys + values + leaves + internal nodes + the small arrays
+    assert k * (2 * 8 + 7 * 8 + 18 * 4) + 4096 < 64 << 20

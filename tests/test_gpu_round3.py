@@ -2,6 +2,7 @@
 reduction) at world size 1 and — where the box has them — 2 ranks; the 2-rank gloo flavour on one device; the per-context option API that
 replaced the library's getenv knobs; the bvh_timings.sampled flag."""
 import ctypes as C
+import importlib.util
 import json
 import os
 import socket
@@ -74,6 +75,30 @@ def test_bench_gloo_two_ranks_on_one_device():
     out = _run_bench(2, {"BVH_BENCH_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["allgather_us"] is not None
     assert out["config"]["tris_per_gpu"] == 200000 and out["value"] > 0
+
+
+def test_bench_dump_outputs(pkg, orc, ctx, tmp_path):
+    """bench.py --dump-outputs DIR (the benchmark's own command line, no launcher): --steps timed builds, then the last one's result as float .npy files,
+    equal to the same build made here (node rows are numbering independent) and to the oracle's sort"""
+    d = tmp_path / "bench"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--tris", "200000", "--steps", "3", "--warmup", "1", "--cpu-sample", "0",
+           "--no-secondary", "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["config"]["builder"] == "HPLOC"
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    tris = pkg.meshgen.uniform(200_000, 1, offset=(0.0, 0.0, 0.0))              # rank 0's mesh
+    here = bench.dump_outputs(pkg.HPLOC().build(ctx, tris).download(), str(tmp_path / "here"))
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+    for name, a in here.items():
+        got = np.load(d / (name + ".npy"))
+        assert got.dtype in (np.float32, np.float64) and got.dtype == a.dtype and np.array_equal(got, a), name
+    fe = orc.front_end(tris, 30)
+    assert np.array_equal(here["sorted_keys"], fe["skeys"].astype(np.float64)) and np.array_equal(here["sorted_vals"], fe["svals"].astype(np.float64))
 
 
 def test_ctx_options_replace_env_knobs(pkg, orc, ctx):
