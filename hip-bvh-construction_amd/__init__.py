@@ -65,6 +65,7 @@ EXPORTS = [
     "bvh_ctx_set_kernel_filter", "bvh_ctx_set_kernel_sampling", "bvh_bvh4_cost", "bvh_checksum", "bvh_ctx_last_collapse_ms", "bvh_batch_create", "bvh_batch_build", "bvh_batch_download", "bvh_batch_destroy",
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
+    "bvh_refit", "bvh_refit_ex",
 ]
 
 
@@ -175,6 +176,8 @@ def lib() -> C.CDLL:
         "bvh_batch_destroy": ([vp], None), "bvh_batch_download": ([vp, C.POINTER(BatchMesh), vp, vp], i32),
         "bvh_ctx_set_option": ([vp, i32, C.c_int64], i32), "bvh_ctx_get_option": ([vp, i32, C.POINTER(C.c_int64)], i32),
         "bvh_abi_version": ([], u32), "bvh_abi_struct_sizes": ([C.POINTER(u32)], None),
+        "bvh_refit": ([vp, C.POINTER(Result), vp, i32, C.POINTER(Timings)], i32),
+        "bvh_refit_ex": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(Timings)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -363,6 +366,36 @@ class _Builder:
         inp = BuildInput(tri_format, morton_bits, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
                          _ptr(indices) if indices is not None else None, n_vertices, 0)
         _check(lib().bvh_build_ex(context.handle, self.ALGO, C.byref(inp), n, C.byref(self.result), C.byref(self.timings)), f"{ALGO_NAMES[self.ALGO]}::build_ex")
+        return self._publish()
+
+    def refit(self, primitives, on_device: bool = False, n: int | None = None) -> "_Builder":
+        """bvh_refit: recompute every box of this builder's tree from new triangle positions (same count, same order), topology kept.
+        ``primitives`` as for ``build``; runs on the context of the last build.  download / checksum / sah_cost / collapse4 / render then see the refit tree."""
+        if self._ctx is None:
+            raise BvhError("refit needs a built tree")
+        if isinstance(primitives, np.ndarray):
+            if primitives.dtype != TRIANGLE:
+                raise BvhError("primitives must have dtype TRIANGLE (64-byte records)")
+            primitives = np.ascontiguousarray(primitives)
+            n = primitives.shape[0]
+            on_device = False
+        elif n is None:
+            raise BvhError("n is required for device inputs")
+        if n != self.result.n_leaves:
+            raise BvhError(f"refit with {n} triangles of a tree over {self.result.n_leaves}")
+        _check(lib().bvh_refit(self._ctx.handle, C.byref(self.result), _ptr(primitives), int(on_device), C.byref(self.timings)),
+               f"{ALGO_NAMES[self.ALGO]}::refit")
+        return self._publish()
+
+    def refit_ex(self, n: int | None = None, tris=None, vertices=None, indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64) -> "_Builder":
+        """bvh_refit_ex: device inputs in any bvh_tri_format (as build_ex; the Morton width is the tree's own)."""
+        if self._ctx is None:
+            raise BvhError("refit needs a built tree")
+        if n is not None and n != self.result.n_leaves:
+            raise BvhError(f"refit with {n} triangles of a tree over {self.result.n_leaves}")
+        inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                         _ptr(indices) if indices is not None else None, n_vertices, 0)
+        _check(lib().bvh_refit_ex(self._ctx.handle, C.byref(self.result), C.byref(inp), C.byref(self.timings)), f"{ALGO_NAMES[self.ALGO]}::refit_ex")
         return self._publish()
 
     def _publish(self) -> "_Builder":

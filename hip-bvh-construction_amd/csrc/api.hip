@@ -83,6 +83,11 @@ struct bvh_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool queue_items_stale = false;   // the classic tile schedule leaves its queue items behind; the overlapped one needs (and leaves) the slots all-zero
     int64_t options[4] = {0, 0, 0, 0}; // bvh_option values (bvh_ctx_set_option); all default 0 = decide by input size / no test knobs
+    // bvh_refit's parent plan of the ctx's own tree, kept in `parent` while nothing rewrote nodes / leaves / parent: every path that writes them (a build, the
+    // bvh_emit_* entry points, a re-allocation, the device-memory helpers, which may be aimed at the arena) bumps tree_serial; the plan is valid for
+    // {plan_serial == tree_serial, plan_n, plan_root}.  plan_serial 0: no plan (a refit of caller-owned arrays made one of ITS tree in `parent`).
+    uint64_t tree_serial = 1, plan_serial = 0;
+    uint32_t plan_n = 0, plan_root = 0;
 };
 
 namespace {
@@ -210,6 +215,7 @@ int ensure_capacity(bvh_ctx* c, uint32_t n) {
     char* p = nullptr;
     HIP_TRY(hipMalloc(&p, total));
     c->arena = p; c->arena_bytes = total; c->cap = n;
+    ++c->tree_serial;
     c->scene_ready = false; c->scene_slot = 0;
     carve(c, p, n, &total);
     HIP_TRY(hipMemsetAsync(c->hploc.dep, 0, (size_t)n * sizeof(u64), c->stream));   // HPLOC dependency words: clean once, builds keep them clean
@@ -391,7 +397,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); }); }
     *out = c;
     return 0;
 }
@@ -520,6 +526,7 @@ int bvh_emit_lbvh_single(bvh_ctx* c, const void* d_prim_aabbs, const uint32_t* d
     if (!c || !d_prim_aabbs || !d_sorted_keys || !d_sorted_vals || !d_nodes || n < 2) return BVH_E_INVALID_ARG;
     Bind b(c->device);
     int r = ensure_capacity(c, n); if (r) return r;
+    ++c->tree_serial;
     r = begin_emit(c); if (r) return r;
     launch_lbvh_single(c->stream, d_prim_aabbs, d_sorted_keys, 32, d_sorted_vals, n, d_nodes, c->hploc.dep, c->small, c->ploc.list0, c->lbvh_queue_capacity, c->hploc.queue_count, false, (int)c->options[BVH_OPT_LBVH_SCHEDULER]);
     r = end_emit(c); if (r) return r;
@@ -532,6 +539,7 @@ int bvh_emit_lbvh_two(bvh_ctx* c, const void* d_prim_aabbs, const uint32_t* d_so
     if (!c || !d_prim_aabbs || !d_sorted_keys || !d_sorted_vals || !d_nodes || n < 2) return BVH_E_INVALID_ARG;
     Bind b(c->device);
     int r = ensure_capacity(c, n); if (r) return r;
+    ++c->tree_serial;
     r = begin_emit(c); if (r) return r;
     launch_lbvh_two(c->stream, d_prim_aabbs, d_sorted_keys, 32, d_sorted_vals, n, d_nodes, c->parent, c->flags, c->hploc.dep, c->small,
                     c->ploc.list0, c->lbvh_queue_capacity, c->hploc.queue_count, false, (int)c->options[BVH_OPT_LBVH_SCHEDULER]);
@@ -543,6 +551,7 @@ int bvh_emit_ploc(bvh_ctx* c, const void* d_prim_aabbs, const uint32_t* d_sorted
     if (!c || !d_prim_aabbs || !d_sorted_vals || !d_nodes || !d_leaves || n < 2) return BVH_E_INVALID_ARG;
     Bind b(c->device);
     int r = ensure_capacity(c, n); if (r) return r;
+    ++c->tree_serial;
     ploc_begin(c->stream, c->ploc, n);
     HIP_TRY(hipGetLastError());
     return run_ploc(c, n, d_nodes, d_leaves, d_prim_aabbs, d_sorted_vals, c->ploc, iterations_out);
@@ -553,6 +562,7 @@ int bvh_emit_hploc(bvh_ctx* c, const void* d_prim_aabbs, const uint32_t* d_sorte
     if (!c || !d_prim_aabbs || !d_sorted_keys || !d_sorted_vals || !d_nodes || !d_leaves || n < 2) return BVH_E_INVALID_ARG;
     Bind b(c->device);
     int r = ensure_capacity(c, n); if (r) return r;
+    ++c->tree_serial;
     r = begin_emit(c); if (r) return r;
     emit_hploc(c, c->stream, d_prim_aabbs, d_sorted_keys, 32, d_sorted_vals, n, d_nodes, d_leaves);
     return end_emit(c);
@@ -572,6 +582,7 @@ static int build_impl(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint
     struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
     uint32_t ploc_iters = 0;
     int r = 0;
+    ++c->tree_serial;                                         // (bvh_refit's cached parent plan no longer describes c->nodes)
     if (prof) HIP_TRY(hipEventRecord(c->ev[0], s));
     // E: CalculateSceneExtents (token CalculateCentroidExtentsTime).  The sort's bookkeeping is cleared here so that the
     // Morton kernel can accumulate the digit histograms.
@@ -675,6 +686,74 @@ int bvh_build_ex(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_t 
     Bind b(c->device);
     int r = ensure_capacity(c, n); if (r) return r;
     return build_impl(c, algo, in, n, out, tm);
+}
+
+// ---- refit (no counterpart in the reference) ----------------------------------------------------------------------------------------------------
+// what bvh_refit may touch is checked before anything is enqueued: an error changes nothing.  The arena is never re-allocated (io may point into it).
+static int refit_check(const bvh_ctx* c, const bvh_result* io) {
+    if (!c || !io) return BVH_E_INVALID_ARG;
+    const uint32_t n = io->n_leaves;
+    if (n < 2 || io->layout > 1u || !io->d_nodes || !io->d_prim_aabbs || !io->d_scene_extent) return BVH_E_INVALID_ARG;
+    if (io->layout == 1u && !io->d_leaves) return BVH_E_INVALID_ARG;
+    if (n > c->cap || io->root >= n - 1) return BVH_E_INVALID_ARG;      // (parent / flags scratch is sized by the capacity: bvh_ctx_reserve first)
+    return 0;
+}
+// stage E into io's prim boxes and scene extent (the result's own extent slot: the other slot and the ctx's scene bookkeeping are untouched), the parent plan
+// unless the ctx's own tree has one, the refit climb.  Timings: ms_extents = stage E, ms_build = plan + climb (bvh_ctx_kernel_times names them apart)
+static int refit_impl(bvh_ctx* c, bvh_result* io, const bvh_build_input* in, bvh_timings* tm) {
+    hipStream_t s = c->stream;
+    const uint32_t n = io->n_leaves;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    const bool prof = c->profiling && sampled;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    if (prof) HIP_TRY(hipEventRecord(c->ev[0], s));
+    int r = stage_extents_fmt(s, in, n, io->d_prim_aabbs, io->d_scene_extent, true, nullptr); if (r) return r;
+    if (prof) HIP_TRY(hipEventRecord(c->ev[1], s));
+    r = begin_emit(c); if (r) return r;
+    const bool own = io->d_nodes == c->nodes;
+    if (!own || c->plan_serial != c->tree_serial || c->plan_n != n || c->plan_root != io->root) {
+        launch_refit_plan(s, io->d_nodes, n, io->root, c->parent);
+        c->plan_serial = own ? c->tree_serial : 0; c->plan_n = n; c->plan_root = io->root;
+    }
+    launch_refit_climb(s, io->d_prim_aabbs, io->d_nodes, io->d_leaves, (int)io->layout, n, c->parent, c->flags);
+    r = end_emit(c); if (r) { c->plan_serial = 0; return r; }
+    if (install.on) c->recorder.mark(s, nullptr);
+    if (prof) HIP_TRY(hipEventRecord(c->ev[4], s));
+    io->d_tris = in->tri_format == BVH_TRI_INDEXED ? in->d_vertices : in->d_tris;
+    if (tm) {
+        std::memset(tm, 0, sizeof *tm);
+        tm->bytes_algorithmic = 200ull * n;          // nominal, 64-byte triangles (DESIGN.md "Refit")
+        tm->sampled = prof ? 1u : 0u;
+        if (prof) {
+            HIP_TRY(hipEventSynchronize(c->ev[4]));
+            HIP_TRY(hipEventElapsedTime(&tm->ms_extents, c->ev[0], c->ev[1]));
+            HIP_TRY(hipEventElapsedTime(&tm->ms_build, c->ev[1], c->ev[4]));
+            tm->ms_total = tm->ms_extents + tm->ms_build;
+        }
+    }
+    return 0;
+}
+
+int bvh_refit(bvh_ctx* c, bvh_result* io, const void* tris, int tris_on_device, bvh_timings* tm) {
+    int r = refit_check(c, io); if (r) return r;
+    if (!tris) return BVH_E_INVALID_ARG;
+    Bind b(c->device);
+    bvh_build_input in; std::memset(&in, 0, sizeof in);
+    in.tri_format = BVH_TRI_PADDED64; in.morton_bits = 30; in.d_tris = tris;
+    if (!tris_on_device) {   // H2D copy into the ctx's staging buffer (not part of the arena), untimed as for a build
+        r = ensure_tris(c, io->n_leaves); if (r) return r;
+        HIP_TRY(hipMemcpyAsync(c->tris, tris, (size_t)io->n_leaves * sizeof(bvh_triangle), hipMemcpyHostToDevice, c->stream));
+        in.d_tris = c->tris;
+    }
+    return refit_impl(c, io, &in, tm);
+}
+
+int bvh_refit_ex(bvh_ctx* c, bvh_result* io, const bvh_build_input* in, bvh_timings* tm) {
+    int r = refit_check(c, io); if (r) return r;
+    if (!in) return BVH_E_INVALID_ARG;
+    r = stage_extents_valid(in); if (r) return r;
+    Bind b(c->device);
+    return refit_impl(c, io, in, tm);
 }
 
 int bvh_to_lbvh_layout(bvh_ctx* c, const bvh_result* in, void* d_out) {
@@ -826,14 +905,14 @@ int bvh_download(bvh_ctx* c, const bvh_result* in, void* h_nodes, void* h_leaves
 int bvh_dev_alloc(bvh_ctx* c, uint64_t bytes, void** out) { if (!c || !out) return BVH_E_INVALID_ARG; Bind b(c->device); return herr(hipMalloc(out, bytes)); }
 int bvh_dev_free(bvh_ctx* c, void* p) { if (!c) return BVH_E_INVALID_ARG; Bind b(c->device); return herr(hipFree(p)); }
 int bvh_dev_upload(bvh_ctx* c, void* d_dst, const void* h_src, uint64_t bytes) {
-    if (!c) return BVH_E_INVALID_ARG; Bind b(c->device);
+    if (!c) return BVH_E_INVALID_ARG; Bind b(c->device); ++c->tree_serial;
     HIP_TRY(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, c->stream)); return herr(hipStreamSynchronize(c->stream)); }
 int bvh_dev_download(bvh_ctx* c, void* h_dst, const void* d_src, uint64_t bytes) {
     if (!c) return BVH_E_INVALID_ARG; Bind b(c->device);
     HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream)); return herr(hipStreamSynchronize(c->stream)); }
 
 int bvh_dev_copy(bvh_ctx* c, void* d_dst, const void* d_src, uint64_t bytes) {   // asynchronous, ordered on the ctx's stream; a kernel, not a runtime copy (misc.hip)
-    if (!c || (bytes && (!d_dst || !d_src))) return BVH_E_INVALID_ARG; Bind b(c->device);
+    if (!c || (bytes && (!d_dst || !d_src))) return BVH_E_INVALID_ARG; Bind b(c->device); ++c->tree_serial;
     launch_copy_bytes(c->stream, d_dst, d_src, (size_t)bytes);
     return herr(hipGetLastError()); }
 

@@ -100,6 +100,29 @@ __device__ __forceinline__ void node_store_plain(bvh2_node* n, u32 left, u32 rig
     q[0] = make_float4(__uint_as_float(left), __uint_as_float(right), b.lx, b.ly);
     q[1] = make_float4(b.lz, b.hx, b.hy, b.hz);
 }
+// The refit walk of one finished node `cur` (its box is in memory) through the global second-arriver protocol: k_refit (the two-pass build's fit) and
+// k_refit_climb (bvh_refit).  The reference counts arrivals (atomicAdd(flags) > 0, src/TwoPassLbvhKernel.h:224) and then re-reads the child links to find
+// the sibling; exchanging the arriving child's index instead hands the sibling to the second arriver directly.  The second arriver resets the word: the
+// array stays all-INVALID.  parent: u32[2n-1] over the index space {internal [0, ni), leaf j at ni + j}, parent[root] = INVALID; a parent index outside
+// [0, ni) also ends the walk (never in a tree).  sib_box(s): the box of sibling s — internal nodes are read with agent-scope loads (written in this launch).
+template <typename SibBox>
+__device__ __forceinline__ void refit_climb(u32 cur, Box box, bvh2_node* nodes, const u32* __restrict__ parent, u32* flags, u32 ni, SibBox sib_box) {
+    u32 p = parent[cur];
+    while (p < ni) {
+        drain_stores();
+        const u32 sib = __hip_atomic_exchange(flags + p, cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (sib == INV) break;
+        st_agent(flags + p, INV);
+        compiler_fence();
+        box = box_union(box, sib_box(sib));
+        node_box_store_agent(nodes + p, box);
+        cur = p; p = parent[p];
+    }
+}
+// LBVH layout: every node, leaves included, is a record of `nodes` written with agent-scope stores before the walker that owns it climbs
+__device__ __forceinline__ void refit_climb(u32 cur, Box box, bvh2_node* nodes, const u32* __restrict__ parent, u32* flags, u32 ni) {
+    refit_climb(cur, box, nodes, parent, flags, ni, [nodes](u32 s) { return node_box_agent(nodes + s); });
+}
 // plain loads / stores (data from an earlier kernel).  Aabb arrays (24-byte stride) and Bvh2Node::aabb (offset 8 of 32) are
 // 8-byte aligned: three 8-byte accesses instead of six 4-byte ones.  PrimRef::aabb sits at offset 4 of a 28-byte record:
 // box_load_u for those.

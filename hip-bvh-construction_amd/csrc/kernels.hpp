@@ -148,6 +148,11 @@ void ploc_reset(hipStream_t s, const PlocScratch& sc, uint32_t n, uint32_t count
 void ploc_enqueue(hipStream_t s, const PlocScratch& sc, uint32_t n, void* d_nodes, void* d_leaves, const void* d_boxes, const uint32_t* d_svals,
                   int first, int count, int parity, bool fresh);
 
+// ---- refit (refit.hip): bvh_refit's two kernels after stage E.  parent: u32[2n-1] plan over {internal [0, n-1), leaf j at n-1+j}; flags: u32[n-1] exchange
+// words, all-INVALID before the climb and left so.  layout 0: leaves are nodes n-1 .. 2n-2; layout 1: d_leaves = PrimRef[n]
+void launch_refit_plan(hipStream_t s, const void* d_nodes, uint32_t n, uint32_t root, uint32_t* d_parent);
+void launch_refit_climb(hipStream_t s, const void* d_prim_boxes, void* d_nodes, void* d_leaves, int layout, uint32_t n, const uint32_t* d_parent, uint32_t* d_flags);
+
 // ---- BVH2 -> BVH4 collapse (collapse.hip)
 constexpr int COLLAPSE_MAX_BATCH = 64;                       // levels per batch of launches (one counter word per level)
 constexpr int COLLAPSE_STATE_WORDS = COLLAPSE_MAX_BATCH;
@@ -176,6 +181,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit();
 
 } // namespace bvh

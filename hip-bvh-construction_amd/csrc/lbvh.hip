@@ -275,28 +275,11 @@ __global__ __launch_bounds__(LBVH_BLOCK) void k_karras(const bvh_aabb* __restric
     parent[lc] = idx; parent[rc] = idx;
 }
 
-// the refit walk of one finished node `cur` (its box is in memory) through the global second-arriver protocol.  The reference counts
-// arrivals (atomicAdd(flags) > 0, :224) and then re-reads the child links to find the sibling; exchanging the arriving child's index
-// instead hands the sibling to the second arriver directly.  The second arriver resets the word: the array stays all-INVALID.
-__device__ __forceinline__ void refit_climb(u32 cur, Box box, bvh2_node* nodes, const u32* __restrict__ parent, u32* flags) {
-    u32 p = parent[cur];
-    while (p != INV) {
-        drain_stores();
-        const u32 sib = __hip_atomic_exchange(flags + p, cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sib == INV) break;
-        st_agent(flags + p, INV);
-        compiler_fence();
-        box = box_union(box, node_box_agent(nodes + sib));
-        node_box_store_agent(nodes + p, box);
-        cur = p; p = parent[p];
-    }
-}
-
 __global__ __launch_bounds__(LBVH_BLOCK) void k_refit(bvh2_node* nodes, const u32* __restrict__ parent, u32* flags, u32 n) {
     const u32 g = bid_x() * LBVH_BLOCK + tid_x();
     if (g >= n) return;
     const u32 cur = n - 1 + g;
-    refit_climb(cur, box_load(&nodes[cur].aabb), nodes, parent, flags);    // leaf box: written by k_karras (previous launch)
+    refit_climb(cur, box_load(&nodes[cur].aabb), nodes, parent, flags, n - 1);    // leaf box: written by k_karras (previous launch)
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------

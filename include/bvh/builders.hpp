@@ -163,6 +163,17 @@ public:
         publish(context, r, t, n);
     }
 
+    // beyond the reference (bvh_refit): the same triangles moved — same count, same order — give the tree built last new boxes, topology kept; then the
+    // tail of build() (collapse + m_cost) as after a build
+    void refit(Context& context, std::vector<Triangle>& primitives) {
+        if (static_cast<u32>(primitives.size()) != m_result.n_leaves) throw std::runtime_error("refit: triangle count differs from the built tree's");
+        bvh_timings t{};
+        check(bvh_refit(context.handle(), &m_result, primitives.data(), 0, &t), "refit");
+        m_triFormat = BVH_TRI_PADDED64;
+        const bvh_result r = m_result;
+        publish(context, r, t, r.n_leaves);
+    }
+
     // X::traverseBvh(Context&): GenerateRays -> the traversal kernel this builder's reference source selects -> RGBA read-back -> perf block.
     void traverseBvh(Context& context) {
         constexpr TraverseFlavour f = flavour<ALGO>();

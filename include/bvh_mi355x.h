@@ -155,6 +155,24 @@ int  bvh_stage_morton_plan(bvh_ctx* ctx, const void* d_scene_extent, int total_b
 int  bvh_sort_pairs64(bvh_ctx* ctx, const uint64_t* d_keys_in, const uint32_t* d_vals_in, uint32_t n,
                       uint64_t* d_keys_out, uint32_t* d_vals_out, int start_bit, int end_bit);
 
+/* ---- refit (no counterpart in the reference) ------------------------------------------------------------------------------------------
+ * Recompute every box of an existing tree from new triangle positions, with the topology kept (deforming / animated meshes: vertices move, connectivity
+ * and ordering stay).  Stage E, then the boxes are unioned bottom-up through the existing child links; Morton codes, sort and hierarchy search are skipped.
+ * io: a result of bvh_build / bvh_build_ex on this ctx, or a caller-filled bvh_result whose arrays are device arrays on the ctx's device.
+ * Written in place: leaf boxes (LBVH layout: nodes n-1 .. 2n-2; PLOC layout: d_leaves[j].aabb), every internal node's aabb, d_prim_aabbs, d_scene_extent;
+ * io->d_tris is set to the triangles read.  Child links, leaf prim indices, root, d_sorted_* and d_morton_keys are not touched (the keys still describe the
+ * mesh the tree was built from).  tris: Triangle[io->n_leaves], host or device, as in bvh_build.  timings: optional, same meaning and sampling rules as for a
+ * build: ms_extents = stage E, ms_build = the refit proper (ms_morton / ms_sort are 0); bvh_ctx_kernel_times reports its kernels as k_refit_plan / k_refit_climb.
+ * Contract: leaf boxes (and d_prim_aabbs) are bit-identical to what stage E writes for the same input; an internal box is the componentwise fminf / fmaxf union
+ * of its two children's boxes, so a refit with the triangles the tree was built from reproduces the build's arrays.
+ * The parent plan of the ctx's own tree is made once and kept until a build (or an emit) rewrites it; caller-owned arrays get a new plan on every call.
+ * Errors (nothing is changed): NULL ctx / io / input, n_leaves < 2, layout not 0 or 1, NULL d_nodes / d_prim_aabbs / d_scene_extent, layout 1 with NULL
+ * d_leaves, root not an internal node, an input format error: BVH_E_INVALID_ARG.  n_leaves larger than the ctx's capacity: BVH_E_INVALID_ARG — a refit
+ * never re-allocates the arena (io may point into it); call bvh_ctx_reserve first.  Asynchronous like a build, except for what the timings need. */
+int  bvh_refit(bvh_ctx* ctx, bvh_result* io, const void* tris, int tris_on_device, bvh_timings* timings /* may be NULL */);
+/* the same on any bvh_tri_format (morton_bits is ignored) */
+int  bvh_refit_ex(bvh_ctx* ctx, bvh_result* io, const bvh_build_input* in, bvh_timings* timings /* may be NULL */);
+
 /* ---- stage-level entry points (one per reference kernel / library call on the path) -------------------------- */
 
 /* CalculateSceneExtents (src/CommonBlocksKernel.h:92-114): Triangle[n] -> Aabb[n] + scene Aabb.
