@@ -144,7 +144,9 @@ typedef struct {
 int  bvh_build_ex(bvh_ctx* ctx, bvh_algo algo, const bvh_build_input* in, uint32_t n, bvh_result* out, bvh_timings* timings /* may be NULL */);
 /* stage E on any input format */
 int  bvh_stage_extents_ex(bvh_ctx* ctx, const bvh_build_input* in, uint32_t n, void* d_prim_aabbs, void* d_scene_extent);
-/* stage M with a total_bits budget (<= 60) into u64 keys; total_bits = 30 reproduces bvh_stage_morton's codes */
+/* stage M with a total_bits budget (3..60) into u64 keys; total_bits = 30 reproduces bvh_stage_morton's codes.  The codes keep the reference's
+ * interleave (X * 4 + Y * 2 + Z) at every budget: one that does not split evenly over the axes (not a multiple of 3 in 3-D, odd in 2-D) sets up to
+ * two bits above total_bits, and degenerate extents wrap as in the reference, so sort the keys on [0, 64) as the builds do. */
 int  bvh_stage_morton64(bvh_ctx* ctx, const void* d_prim_aabbs, uint32_t n, const void* d_scene_extent, uint64_t* d_keys, int total_bits);
 /* The per-scene bit plan of stage M exactly as the device evaluates it (src/CommonBlocksKernel.h:162-275: axis order by extent, pre-bits from (int)log2f of the
  * extent ratios, the bit budget): plan_out = {axis[3], bits[3], pre[2], pre_sum, swap}.  total_bits 30 = bvh_stage_morton, <= 60 = bvh_stage_morton64.  A host

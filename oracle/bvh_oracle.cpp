@@ -293,14 +293,15 @@ void orc_primrefs(const void* tris, u32 n, void* refs_out) {
     for (u32 i = 0; i < n; ++i) { out[i].prim = i; out[i].b = tri_box(t[i]); }
 }
 
-// ---- Stage M.  plan_out: 9 ints {axis[3], bits[3], pre[2], pre_sum} + swap = 10 ints
-void orc_morton_plan(const void* scene, int* plan_out) {
+// ---- Stage M.  plan_out: 9 ints {axis[3], bits[3], pre[2], pre_sum} + swap = 10 ints; total_bits: the code's bit budget (3..60, as bvh_stage_morton_plan)
+void orc_morton_plan_bits(const void* scene, int total_bits, int* plan_out) {
     const Box* s = (const Box*)scene;
     F3 e = { s->hi.x - s->lo.x, s->hi.y - s->lo.y, s->hi.z - s->lo.z };
-    MortonPlan m = morton_plan(e);
+    MortonPlan m = morton_plan(e, (u32)total_bits);
     for (int i = 0; i < 3; ++i) { plan_out[i] = m.axis[i]; plan_out[3 + i] = m.bits[i]; }
     plan_out[6] = m.pre[0]; plan_out[7] = m.pre[1]; plan_out[8] = m.pre_sum; plan_out[9] = m.swap;
 }
+void orc_morton_plan(const void* scene, int* plan_out) { orc_morton_plan_bits(scene, 30, plan_out); }
 
 // src/CommonBlocksKernel.h:374-398: centre = (max+min)*0.5f; p = (centre - scene.min) / extent (f32 divides); value = index
 void orc_morton_codes(const void* boxes, u32 stride_bytes, u32 box_offset_bytes, u32 n, const void* scene, u32* keys_out, u32* vals_out) {

@@ -48,6 +48,7 @@ def lib() -> C.CDLL:
         L.orc_prim_bounds.argtypes = [vp, u32, vp, vp]
         L.orc_primrefs.argtypes = [vp, u32, vp]
         L.orc_morton_plan.argtypes = [vp, vp]
+        L.orc_morton_plan_bits.argtypes = [vp, C.c_int, vp]
         L.orc_morton_codes.argtypes = [vp, u32, u32, u32, vp, vp, vp]
         L.orc_sort_pairs.argtypes = [vp, vp, u32, vp, vp]
         L.orc_morton_codes64.argtypes = [vp, u32, u32, u32, vp, C.c_int, vp]
@@ -92,9 +93,10 @@ def primrefs(tris: np.ndarray) -> np.ndarray:
     return refs
 
 
-def morton_plan(scene: np.ndarray) -> dict:
+def morton_plan(scene: np.ndarray, total_bits: int = 30) -> dict:
+    """the per-scene bit plan for a total_bits budget (30: the reference's codes; up to 60 for u64 keys), as bvh_stage_morton_plan lays it out"""
     p = np.zeros(10, dtype=np.int32)
-    lib().orc_morton_plan(scene.ctypes.data, p.ctypes.data)
+    lib().orc_morton_plan_bits(scene.ctypes.data, int(total_bits), p.ctypes.data)
     return {"axis": p[0:3].tolist(), "bits": p[3:6].tolist(), "pre": p[6:8].tolist(), "pre_sum": int(p[8]), "swap": int(p[9])}
 
 
