@@ -113,7 +113,7 @@ struct HplocScratch {
     uint32_t* zero_parent;   // u32[1]
     uint32_t* queue_pc;      // u32[queue_capacity]   (block-local mode: nodes ready for k_hploc_ext)
     uint64_t* queue_rng;     // u64[queue_capacity]
-    uint32_t* queue_count;   // u32[64 * 32 + 32]     (one padded head per sub-queue + the overlapped schedule's "tiles done" word)
+    uint32_t* queue_count;   // u32[64 * 32]          (one padded head per sub-queue)
     size_t    queue_capacity;
     const void* leaf_tris = nullptr;   // build path, 64-byte triangles only: the emitters stage a leaf's box from its triangle (one aligned 64-byte line per
                                        // leaf) instead of from the 24-byte box array (a box straddles two 64-byte lines one time in four); nullptr: boxes
@@ -121,14 +121,10 @@ struct HplocScratch {
 size_t hploc_queue_capacity(uint32_t n);
 uint32_t hploc_block_tile();
 uint32_t hploc_head_words();     // words of queue_count every build starts from zero (the build path's first kernel clears them)
-// Overlapped schedule of the tile scheduler (hploc.hip "k_hploc_live"): the external climb runs on `side` beside the tile kernel.  queue_pc / queue_rng must be
-// all-zero before the build and are left all-zero by it (the classic schedule leaves its items behind: api.hip keeps track).
-struct HplocLive { hipStream_t side; hipEvent_t fork, join; };
 void launch_hploc(hipStream_t s, const void* d_boxes, const void* d_skeys, int key_bits, const uint32_t* d_svals, uint32_t n,
                   void* d_nodes, void* d_leaves, const HplocScratch& sc);
 void launch_hploc_block(hipStream_t s, const void* d_boxes, const void* d_skeys, int key_bits, const uint32_t* d_svals, uint32_t n,
-                        void* d_nodes, void* d_leaves, const HplocScratch& sc, bool heads_cleared = false /* sc.queue_count is already zero */,
-                        const HplocLive* live = nullptr /* non-null with a side stream: the overlapped schedule */);
+                        void* d_nodes, void* d_leaves, const HplocScratch& sc, bool heads_cleared = false /* sc.queue_count is already zero */);
 struct PlocScratch {
     void*     list0;         // 32-byte cluster entries {id, box} x n (ping)
     void*     list1;         // pong

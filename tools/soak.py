@@ -30,7 +30,7 @@ def soak(pkg, orc, ctx, budget: float, seed: int, sizes=SIZES, max_random: int =
             d_tris = ctx.upload(tris)
             fe = orc.front_end(tris, morton_bits=bits) if n <= 1_200_000 else None
             for algo in (0, 1, 2, 3):
-                for mode in ((("async", "single"), ("block", "block"), ("live", "block")) if algo == 3 else (("async", "single"), ("block", "block"))) if algo != 2 else (("", ""),):
+                for mode in (("async", "single"), ("block", "block")) if algo != 2 else (("", ""),):
                     if time.time() > t_end + 30: break
                     ctx.set_option("hploc", mode[0] or "auto"); ctx.set_option("lbvh", mode[1] or "auto")
                     if algo == 2: ctx.set_option("ploc", int(rng.integers(0, 2)))          # static chunk ids / tickets only
