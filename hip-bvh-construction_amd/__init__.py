@@ -29,6 +29,7 @@ PRIMREF = np.dtype([("prim", "<u4"), ("min", "<f4", 3), ("max", "<f4", 3)])
 BVH4_NODE = np.dtype([("aabb", AABB, 4), ("child", "<u4", 4), ("parent", "<u4"), ("count", "<u4"), ("pad", "<u4", 2)])
 PRIM_NODE = np.dtype([("prim", "<u4"), ("parent", "<u4")])
 RAY = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("tmin", "<f4"), ("tmax", "<f4")])
+HIT = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")])      # bvh_hit (bvh_intersect)
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
 TRANSFORMATION = np.dtype([("translation", "<f4", 3), ("pad", "<f4"), ("scale", "<f4", 3), ("pad1", "<f4"), ("quat", "<f4", 4), ("pad2", "<f4", 4)])
 assert RAY.itemsize == 32 and CAMERA.itemsize == 64 and TRANSFORMATION.itemsize == 64
@@ -65,7 +66,7 @@ EXPORTS = [
     "bvh_ctx_set_kernel_filter", "bvh_ctx_set_kernel_sampling", "bvh_bvh4_cost", "bvh_checksum", "bvh_ctx_last_collapse_ms", "bvh_batch_create", "bvh_batch_build", "bvh_batch_download", "bvh_batch_destroy",
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
-    "bvh_refit", "bvh_refit_ex",
+    "bvh_refit", "bvh_refit_ex", "bvh_intersect",
 ]
 
 
@@ -100,6 +101,8 @@ class BatchReport(C.Structure):
 
 
 TRI_PADDED64, TRI_PACKED36, TRI_INDEXED = 0, 1, 2
+QUERY_CLOSEST, QUERY_ANY = 0, 1      # bvh_query_kind
+_QUERY_IDS = {"closest": QUERY_CLOSEST, "any": QUERY_ANY}
 ABI_VERSION = 4                      # BVH_ABI_VERSION of include/bvh_mi355x.h this binding was written against
 # bvh_option (bvh_ctx_set_option) and the names this harness accepts for the values
 OPT_HPLOC_SCHEDULER, OPT_LBVH_SCHEDULER, OPT_SORT_TEST_KNOBS, OPT_PLOC_SCHEDULER = 0, 1, 2, 3
@@ -178,6 +181,7 @@ def lib() -> C.CDLL:
         "bvh_abi_version": ([], u32), "bvh_abi_struct_sizes": ([C.POINTER(u32)], None),
         "bvh_refit": ([vp, C.POINTER(Result), vp, i32, C.POINTER(Timings)], i32),
         "bvh_refit_ex": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(Timings)], i32),
+        "bvh_intersect": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -397,6 +401,39 @@ class _Builder:
                          _ptr(indices) if indices is not None else None, n_vertices, 0)
         _check(lib().bvh_refit_ex(self._ctx.handle, C.byref(self.result), C.byref(inp), C.byref(self.timings)), f"{ALGO_NAMES[self.ALGO]}::refit_ex")
         return self._publish()
+
+    def intersect(self, rays, query="closest", tris=None, vertices=None, indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64,
+                  n_rays: int | None = None) -> np.ndarray:
+        """bvh_intersect on this builder's tree: ``rays`` a host RAY array or a device buffer (DeviceBuffer / int address, with ``n_rays``); returns a host
+        HIT array.  query "closest" / "any" (or QUERY_*).  Triangles: tree's d_tris (Triangle[n]) unless tris / vertices / indices give device inputs in
+        ``tri_format`` as for build_ex."""
+        if self._ctx is None:
+            raise BvhError("intersect needs a built tree")
+        ctx = self._ctx
+        q = _QUERY_IDS[query] if isinstance(query, str) else int(query)
+        own = None
+        if isinstance(rays, np.ndarray):
+            if rays.dtype != RAY:
+                raise BvhError("rays must have dtype RAY (32-byte records)")
+            n_rays = rays.shape[0]
+            own = rays = ctx.upload(np.ascontiguousarray(rays)) if n_rays else None
+        elif n_rays is None:
+            n_rays = rays.nbytes // RAY.itemsize if isinstance(rays, DeviceBuffer) else None
+            if n_rays is None:
+                raise BvhError("n_rays is required for device rays")
+        inp = None
+        if tris is not None or vertices is not None or indices is not None:
+            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                             _ptr(indices) if indices is not None else None, n_vertices, 0)
+        hits = ctx.alloc(max(n_rays, 1) * HIT.itemsize)
+        try:
+            _check(lib().bvh_intersect(ctx.handle, C.byref(self.result), C.byref(inp) if inp is not None else None, _ptr(rays) if rays is not None else None,
+                                       n_rays, hits.ptr, q), f"{ALGO_NAMES[self.ALGO]}::intersect")
+            return hits.download(HIT, n_rays)
+        finally:
+            hits.free()
+            if own is not None:
+                own.free()
 
     def _publish(self) -> "_Builder":
         r, t = self.result, self.timings

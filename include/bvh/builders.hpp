@@ -159,7 +159,7 @@ public:
     void build(Context& context, const bvh_build_input& input, u32 n) {
         bvh_result r{}; bvh_timings t{};
         check(bvh_build_ex(context.handle(), ALGO, &input, n, &r, &t), "build_ex");
-        m_triFormat = input.tri_format;
+        m_triFormat = input.tri_format; m_input = input;
         publish(context, r, t, n);
     }
 
@@ -172,6 +172,12 @@ public:
         m_triFormat = BVH_TRI_PADDED64;
         const bvh_result r = m_result;
         publish(context, r, t, r.n_leaves);
+    }
+
+    // beyond the reference (bvh_intersect): closest-hit / any-hit queries of device rays against the tree built (or refit) last, on the triangles it was built from;
+    // asynchronous on the context's stream like the C entry point
+    void intersect(Context& context, const bvh_ray* d_rays, u32 n, bvh_hit* d_hits, bvh_query_kind kind) {
+        check(bvh_intersect(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, d_rays, n, d_hits, static_cast<int>(kind)), "intersect");
     }
 
     // X::traverseBvh(Context&): GenerateRays -> the traversal kernel this builder's reference source selects -> RGBA read-back -> perf block.
@@ -244,6 +250,7 @@ private:
         m_cost = static_cast<float>(c4);
     }
     u32 m_triFormat = BVH_TRI_PADDED64;
+    bvh_build_input m_input{};           // the device input of the last build_ex (intersect reads its triangles when they are not 64-byte records)
 public:
     // the reference's public members (src/Hploc.h:19-32, src/TwoPassLbvh.h:19-31)
     DeviceView<Triangle> d_triangleBuff;                                   // (bound for 64-byte Triangle inputs only)

@@ -1,6 +1,7 @@
 /* types.h — POD layouts of the BVH build path.  Binary-compatible with the reference's src/Common.h:
  *   Aabb      24 B  (src/Common.h:310-416)      Triangle  64 B, alignas(64), 36-B payload (src/Common.h:429-434)
  *   Bvh2Node  32 B, alignas(32) (src/Common.h:436-441)      PrimRef   28 B (src/Common.h:574-578)
+ *   Ray       32 B, alignas(32) (src/Common.h:533-539; the record bvh_generate_rays writes)      bvh_hit 16 B (bvh_intersect's output, no counterpart)
  * Usable from C, C++ and HIP device code. */
 #ifndef BVH_TYPES_H
 #define BVH_TYPES_H
@@ -21,12 +22,16 @@ typedef struct { bvh_float3 min, max; } bvh_aabb;
 typedef struct BVH_ALIGNAS(64) { bvh_float3 v1, v2, v3; } bvh_triangle;
 typedef struct BVH_ALIGNAS(32) { uint32_t left, right; bvh_aabb aabb; } bvh2_node;
 typedef struct { uint32_t prim_idx; bvh_aabb aabb; } bvh_primref;
+typedef struct BVH_ALIGNAS(32) { bvh_float3 origin, direction; float tmin, tmax; } bvh_ray;
+typedef struct { float t, u, v; uint32_t prim_idx; } bvh_hit;
 
 #ifdef __cplusplus
 static_assert(sizeof(bvh_aabb) == 24, "Aabb is 24 bytes");
 static_assert(sizeof(bvh_triangle) == 64, "Triangle is 64 bytes");
 static_assert(sizeof(bvh2_node) == 32, "Bvh2Node is 32 bytes");
 static_assert(sizeof(bvh_primref) == 28, "PrimRef is 28 bytes");
+static_assert(sizeof(bvh_ray) == 32, "Ray is 32 bytes");
+static_assert(sizeof(bvh_hit) == 16, "bvh_hit is 16 bytes");
 #endif
 
 #endif

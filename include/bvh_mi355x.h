@@ -175,6 +175,35 @@ int  bvh_refit(bvh_ctx* ctx, bvh_result* io, const void* tris, int tris_on_devic
 /* the same on any bvh_tri_format (morton_bits is ignored) */
 int  bvh_refit_ex(bvh_ctx* ctx, bvh_result* io, const bvh_build_input* in, bvh_timings* timings /* may be NULL */);
 
+/* ---- ray queries (no counterpart in the reference) -----------------------------------------------------------------------------------
+ * Which triangle does each ray hit first (BVH_QUERY_CLOSEST), or does it hit any (BVH_QUERY_ANY)?  One bvh_hit per ray: d_hits[i] answers d_rays[i].
+ * tree: a result of bvh_build / bvh_build_ex / bvh_refit on this ctx, or a caller-filled bvh_result whose arrays are device arrays on the ctx's device (for instance a
+ * tree read back with bvh_batch_download and uploaded again).  Both layouts are read as they are (no bvh_to_lbvh_layout copy): layout 0 = Bvh2Node[2n-1] with leaf j at
+ * node n-1+j; layout 1 = Bvh2Node[n-1] + PrimRef[n], a child >= n-1 is leaf child-(n-1).  Read: root, n_leaves, layout, d_nodes, d_leaves, d_tris; nothing is written
+ * to the tree.  The arrays must form a tree; a primitive or child index out of range is never followed (the primitive is skipped, the child treated as empty), and
+ * arrays that are not a tree end in finite time with unspecified hits.  There is no depth limit: rays whose short stack would overflow are finished by a stackless pass.
+ * tris: the triangles, any bvh_tri_format, validated as by bvh_build_ex (morton_bits is ignored; INDEXED indices >= n_vertices are read as vertex 0).  NULL:
+ * tree->d_tris is read as Triangle[n_leaves] — a bvh_result does not record the format it was built from, so trees built from packed or indexed input pass `tris`.
+ * Hit test: the reference's intersectTriangle (src/Common.h:516-531) without a transform, in f32 operation for operation: iu, iv, iw, it.  A hit is accepted iff
+ * iu > 0 && iv > 0 && iw > 0 && tmin < it < tmax.  The test is two-sided (either winding is hit); a ray through an edge or a vertex exactly (an iu, iv or iw of 0)
+ * misses.  Directions need not be normalised: t is measured in units of `direction`.
+ * BVH_QUERY_CLOSEST: the accepted hit with the smallest (t, prim_idx), compared lexicographically — the answer does not depend on the builder, the layout, the
+ * traversal order or the input format.  BVH_QUERY_ANY: some accepted hit (which one is unspecified; traversal stops at the first), t / u / v exactly as the
+ * formula gives them for that primitive.  A hit is written as {it, iu, iv, prim_idx}; a miss as {t = ray.tmax, u = 0, v = 0, prim_idx = BVH_INVALID}.  Rays with a
+ * NaN component, or with !(tmin < tmax), miss.  Zero direction components and origins on a box plane are handled.
+ * Box tests are conservative: a subtree is culled only when it cannot hold an accepted hit of a well-conditioned ray (DESIGN.md §8b states the margins: every box
+ * grows on every axis by 2^-16 times its largest |coordinate|, slab interval ends widen by 2^-20 relative; "well-conditioned": every accepted hit's point o + t*d
+ * lies in its triangle's box grown by half that growth).
+ * Errors (nothing is written): NULL ctx / tree / d_rays / d_hits, n_leaves < 2, layout not 0 or 1, NULL d_nodes, layout 1 with NULL d_leaves, root not an internal
+ * node, no triangles (tris NULL and tree->d_tris NULL) or a tris format error, query not 0 or 1, overlapping d_rays / d_hits ranges: BVH_E_INVALID_ARG.  n_leaves
+ * larger than the ctx's capacity: BVH_E_INVALID_ARG — a query never re-allocates the arena (the tree may live in it); call bvh_ctx_reserve first.  n_rays == 0: 0,
+ * nothing is touched.
+ * Asynchronous on the ctx's stream, no read-back.  bvh_ctx_kernel_times reports k_intersect, k_intersect_deep and, when the parent plan of the stackless pass is made,
+ * k_refit_plan.  The plan of the ctx's own tree is made once and kept as for bvh_refit; caller-owned arrays get a new plan on every call. */
+typedef enum { BVH_QUERY_CLOSEST = 0, BVH_QUERY_ANY = 1 } bvh_query_kind;
+int  bvh_intersect(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
+                   const bvh_ray* d_rays, uint32_t n_rays, bvh_hit* d_hits, int query /* bvh_query_kind */);
+
 /* ---- stage-level entry points (one per reference kernel / library call on the path) -------------------------- */
 
 /* CalculateSceneExtents (src/CommonBlocksKernel.h:92-114): Triangle[n] -> Aabb[n] + scene Aabb.
