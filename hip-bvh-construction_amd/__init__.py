@@ -66,7 +66,7 @@ EXPORTS = [
     "bvh_ctx_set_kernel_filter", "bvh_ctx_set_kernel_sampling", "bvh_bvh4_cost", "bvh_checksum", "bvh_ctx_last_collapse_ms", "bvh_batch_create", "bvh_batch_build", "bvh_batch_download", "bvh_batch_destroy",
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
-    "bvh_refit", "bvh_refit_ex", "bvh_intersect",
+    "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
 ]
 
 
@@ -182,6 +182,7 @@ def lib() -> C.CDLL:
         "bvh_refit": ([vp, C.POINTER(Result), vp, i32, C.POINTER(Timings)], i32),
         "bvh_refit_ex": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(Timings)], i32),
         "bvh_intersect": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
+        "bvh_optimize": ([vp, C.POINTER(Result), u32, C.POINTER(Timings)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -400,6 +401,14 @@ class _Builder:
         inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
                          _ptr(indices) if indices is not None else None, n_vertices, 0)
         _check(lib().bvh_refit_ex(self._ctx.handle, C.byref(self.result), C.byref(inp), C.byref(self.timings)), f"{ALGO_NAMES[self.ALGO]}::refit_ex")
+        return self._publish()
+
+    def optimize(self, rounds: int = 3) -> "_Builder":
+        """bvh_optimize: lower this builder's tree's SAH in place by treelet restructuring (``rounds`` 1 .. 8), on the context of the last build.
+        download / checksum / sah_cost / intersect / refit / collapse4 / render then see the optimised tree."""
+        if self._ctx is None:
+            raise BvhError("optimize needs a built tree")
+        _check(lib().bvh_optimize(self._ctx.handle, C.byref(self.result), int(rounds), C.byref(self.timings)), f"{ALGO_NAMES[self.ALGO]}::optimize")
         return self._publish()
 
     def intersect(self, rays, query="closest", tris=None, vertices=None, indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64,

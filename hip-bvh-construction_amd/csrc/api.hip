@@ -368,7 +368,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); warm_optimize(); }); }
     *out = c;
     return 0;
 }
@@ -756,6 +756,47 @@ int bvh_intersect(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tri
     }
     if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
     if (install.on) c->recorder.mark(s, nullptr);
+    return 0;
+}
+
+// ---- tree optimisation (no counterpart in the reference) ----------------------------------------------------------------------------------------
+// every argument is checked before anything is enqueued: an error writes nothing.  The arena is never re-allocated (io may point into it).  The rounds keep
+// parent[] right for the new topology, so the cached plan of the ctx's own tree stays valid (tree_serial is not bumped); caller-owned arrays leave a plan of
+// THEIR tree in `parent`, which the ctx's own tree does not use (plan_serial 0, as after a refit of caller-owned arrays).
+int bvh_optimize(bvh_ctx* c, bvh_result* io, uint32_t rounds, bvh_timings* tm) {
+    if (!c || !io) return BVH_E_INVALID_ARG;
+    const uint32_t n = io->n_leaves;
+    if (n < 2 || io->layout > 1u || !io->d_nodes || (io->layout == 1u && !io->d_leaves) || io->root >= n - 1) return BVH_E_INVALID_ARG;
+    if (rounds < 1u || rounds > 8u) return BVH_E_INVALID_ARG;
+    if (n > c->cap) return BVH_E_INVALID_ARG;                 // (parent / flags scratch is sized by the capacity: bvh_ctx_reserve first)
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    const bool prof = c->profiling && sampled;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    if (prof) HIP_TRY(hipEventRecord(c->ev[1], s));
+    int r = begin_emit(c); if (r) return r;
+    const bool own = io->d_nodes == c->nodes;
+    if (!own || c->plan_serial != c->tree_serial || c->plan_n != n || c->plan_root != io->root) {
+        launch_refit_plan(s, io->d_nodes, n, io->root, c->parent);
+        c->plan_serial = own ? c->tree_serial : 0; c->plan_n = n; c->plan_root = io->root;
+    }
+    uint32_t ran = 0;
+    for (uint32_t k = 0; k < rounds && (7u << k) <= n; ++k, ++ran)       // (a round whose gamma exceeds n has no treelet root: not launched)
+        launch_optimize(s, io->d_nodes, io->d_leaves, (int)io->layout, n, 7u << k, c->parent, c->flags);
+    r = end_emit(c); if (r) { c->plan_serial = 0; return r; }
+    if (install.on) c->recorder.mark(s, nullptr);
+    if (prof) HIP_TRY(hipEventRecord(c->ev[4], s));
+    if (tm) {
+        std::memset(tm, 0, sizeof *tm);
+        tm->bytes_algorithmic = 80ull * n * ran;     // nominal
+        tm->sampled = prof ? 1u : 0u;
+        if (prof) {
+            HIP_TRY(hipEventSynchronize(c->ev[4]));
+            HIP_TRY(hipEventElapsedTime(&tm->ms_build, c->ev[1], c->ev[4]));
+            tm->ms_total = tm->ms_build;
+        }
+    }
     return 0;
 }
 

@@ -149,6 +149,10 @@ void ploc_enqueue(hipStream_t s, const PlocScratch& sc, uint32_t n, void* d_node
 void launch_refit_plan(hipStream_t s, const void* d_nodes, uint32_t n, uint32_t root, uint32_t* d_parent);
 void launch_refit_climb(hipStream_t s, const void* d_prim_boxes, void* d_nodes, void* d_leaves, int layout, uint32_t n, const uint32_t* d_parent, uint32_t* d_flags);
 
+// ---- tree optimisation (optimize.hip): one round of bvh_optimize's treelet restructuring (treelet roots: nodes with >= gamma leaves).  d_parent: the plan of
+// launch_refit_plan, kept right (the rebuild rewrites the parents of what it moves); d_flags: u32[n-1] exchange words, all-INVALID before the launch and left so
+void launch_optimize(hipStream_t s, void* d_nodes, const void* d_leaves, int layout, uint32_t n, uint32_t gamma, uint32_t* d_parent, uint32_t* d_flags);
+
 // ---- ray queries (query.hip): bvh_intersect's two kernels.  k_intersect (short stack) and k_intersect_deep (stackless re-traversal of the rays it marked, through
 // the parent plan of launch_refit_plan; returns at once while *d_overflow == 0).  d_overflow: one word, zeroed before the launch.  Triangles: a validated
 // bvh_build_input's fields (tri_format, d_tris, d_vertices, d_indices, n_vertices)
@@ -184,6 +188,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query(); void warm_optimize();
 
 } // namespace bvh

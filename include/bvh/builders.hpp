@@ -174,6 +174,15 @@ public:
         publish(context, r, t, r.n_leaves);
     }
 
+    // beyond the reference (bvh_optimize): lower the SAH of the tree built (or refit) last by treelet restructuring, in place; then the tail of build()
+    // (collapse + m_cost) as after a build
+    void optimize(Context& context, u32 rounds = 3) {
+        bvh_timings t{};
+        check(bvh_optimize(context.handle(), &m_result, rounds, &t), "optimize");
+        const bvh_result r = m_result;
+        publish(context, r, t, r.n_leaves);
+    }
+
     // beyond the reference (bvh_intersect): closest-hit / any-hit queries of device rays against the tree built (or refit) last, on the triangles it was built from;
     // asynchronous on the context's stream like the C entry point
     void intersect(Context& context, const bvh_ray* d_rays, u32 n, bvh_hit* d_hits, bvh_query_kind kind) {

@@ -204,6 +204,37 @@ typedef enum { BVH_QUERY_CLOSEST = 0, BVH_QUERY_ANY = 1 } bvh_query_kind;
 int  bvh_intersect(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
                    const bvh_ray* d_rays, uint32_t n_rays, bvh_hit* d_hits, int query /* bvh_query_kind */);
 
+/* ---- tree optimisation (no counterpart in the reference) ---------------------------------------------------------------------------------
+ * Lower a built tree's SAH by treelet restructuring (Karras & Aila, HPG 2013): bottom-up, every treelet of 7 entries whose root holds enough leaves is replaced
+ * by its SAH-optimal topology over the same entries.  The fast LBVH builds come out close to HPLOC quality; PLOC++ / HPLOC trees gain a few percent.
+ * io: any tree bvh_refit / bvh_intersect accept — a result of bvh_build / bvh_build_ex / bvh_refit / bvh_optimize on this ctx, or a caller-filled bvh_result of
+ * device arrays on the ctx's device.  Read: root, n_leaves, layout, d_nodes, d_leaves.  Written in place: only the child links and boxes of internal nodes
+ * [0, n-1).  Not written: leaf records (layout 0: nodes n-1 .. 2n-2; layout 1: d_leaves), root, d_prim_aabbs, d_scene_extent, d_sorted_*, d_morton_keys,
+ * d_tris.  The set of internal node indices is unchanged; the root's box keeps its value.  After an optimise an LBVH-layout internal node no longer
+ * corresponds to a split position of d_sorted_keys.
+ * Algorithm (f32 throughout, area = Aabb::area without contraction, unions fminf / fmaxf, comparisons IEEE <).  Round r = 0 .. rounds-1,
+ * gamma = 7 << r; a node is processed after every internal node of its subtree; an internal node N whose subtree holds >= gamma leaves is a treelet root:
+ *   formation: T = [left(N), right(N)]; while |T| < 7, the internal entry of T with the largest stored-box area (the first internal entry starts the scan, a
+ *     later one wins only if strictly larger: ties go to the earliest position) is replaced in place by its left child and its right child is appended; the
+ *     picked nodes are E (expansion order).
+ *   current cost: c_cur(x) = area(x) + (c_cur(left x) + c_cur(right x)) over N and E, 0 for the entries of T.
+ *   DP over the subsets S of {0..6}: B(S) = union of the entries' boxes in increasing bit order; c(S) = 0 for a singleton, else area(B(S)) + the smallest
+ *     c(P) + c(S \ P) over the proper subsets P of S that hold S's lowest bit, in increasing mask order (the first P starts, a later one wins only if strictly smaller).
+ *   decision: restructure iff c(all) < c_cur(N) — NaN or infinite costs keep the treelet byte for byte.
+ *   rebuild: preorder from N (which keeps its index and its box); for the recorded partition {P, Q = S \ P}, P first, a singleton is its entry and a larger
+ *     subset takes the next unused index of E in ascending order; node = {left = node(P), right = node(Q), box B(S)}.
+ * What a treelet becomes depends only on its subtree, which is final when its root is processed: the result does not depend on scheduling, and a tree's SAH
+ * never rises.  Trees with fewer than 7 leaves come back unchanged.  With NaN boxes the output is still a tree over the same leaves.
+ * rounds: 1 .. 8 (3 is the usual choice).  timings: optional, sampled as for a build; ms_build = the optimise, the other stage times are 0; bvh_ctx_kernel_times
+ * reports k_optimize (one launch per round whose gamma is <= n_leaves) and, when the parent plan is made, k_refit_plan.
+ * The ctx's own tree keeps the parent plan of bvh_refit / bvh_intersect valid (the rounds rewrite parent[] as they move nodes); caller-owned arrays get a new
+ * plan on every call.  A later bvh_refit refits the new topology; bvh_intersect closest hits do not change; bvh_collapse4, bvh_to_lbvh_layout, bvh_sah_cost
+ * and bvh_checksum read the result as any tree.
+ * Errors (nothing is written or enqueued): NULL ctx / io, n_leaves < 2, layout not 0 or 1, NULL d_nodes, layout 1 with NULL d_leaves, root not an internal
+ * node, rounds outside [1, 8]: BVH_E_INVALID_ARG.  n_leaves larger than the ctx's capacity: BVH_E_INVALID_ARG — an optimise never re-allocates the arena (io
+ * may point into it); call bvh_ctx_reserve first.  Asynchronous on the ctx's stream, except for what the timings need. */
+int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* timings /* may be NULL */);
+
 /* ---- stage-level entry points (one per reference kernel / library call on the path) -------------------------- */
 
 /* CalculateSceneExtents (src/CommonBlocksKernel.h:92-114): Triangle[n] -> Aabb[n] + scene Aabb.
