@@ -14,6 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -30,9 +31,11 @@ BVH4_NODE = np.dtype([("aabb", AABB, 4), ("child", "<u4", 4), ("parent", "<u4"),
 PRIM_NODE = np.dtype([("prim", "<u4"), ("parent", "<u4")])
 RAY = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("tmin", "<f4"), ("tmax", "<f4")])
 HIT = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")])      # bvh_hit (bvh_intersect)
+INSTANCE = np.dtype([("object_to_world", "<f4", 12), ("blas", "<u4"), ("reserved", "<u4", 3)])                 # bvh_instance (row-major 3x4)
+INSTANCE_HIT = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4", 3)])   # bvh_instance_hit
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
 TRANSFORMATION = np.dtype([("translation", "<f4", 3), ("pad", "<f4"), ("scale", "<f4", 3), ("pad1", "<f4"), ("quat", "<f4", 4), ("pad2", "<f4", 4)])
-assert RAY.itemsize == 32 and CAMERA.itemsize == 64 and TRANSFORMATION.itemsize == 64
+assert RAY.itemsize == 32 and CAMERA.itemsize == 64 and TRANSFORMATION.itemsize == 64 and INSTANCE.itemsize == 64 and INSTANCE_HIT.itemsize == 32
 
 
 def qt_rotation(axis_angle):
@@ -67,6 +70,7 @@ EXPORTS = [
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
+    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas",
 ]
 
 
@@ -114,6 +118,11 @@ class BuildInput(C.Structure):
     """bvh_build_input: device pointers; tri_format TRI_*, morton_bits 30 / 60"""
     _fields_ = [("tri_format", C.c_uint32), ("morton_bits", C.c_uint32), ("d_tris", C.c_void_p), ("d_vertices", C.c_void_p),
                 ("d_indices", C.c_void_p), ("n_vertices", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Blas(C.Structure):
+    """bvh_blas: a bottom-level tree + its triangles (tris.tri_format TRI_PADDED64 with d_tris None: tree.d_tris is Triangle[n_leaves])"""
+    _fields_ = [("tree", Result), ("tris", BuildInput)]
 
 
 def build_native(verbose: bool = False) -> str:
@@ -183,6 +192,12 @@ def lib() -> C.CDLL:
         "bvh_refit_ex": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(Timings)], i32),
         "bvh_intersect": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_optimize": ([vp, C.POINTER(Result), u32, C.POINTER(Timings)], i32),
+        "bvh_build_boxes": ([vp, i32, vp, u32, i32, C.POINTER(Result), C.POINTER(Timings)], i32),
+        "bvh_scene_create": ([vp, C.POINTER(vp)], i32), "bvh_scene_destroy": ([vp], None),
+        "bvh_scene_build": ([vp, i32, C.POINTER(Blas), u32, vp, u32, i32, C.POINTER(Timings)], i32),
+        "bvh_scene_update": ([vp, vp, i32, C.POINTER(Timings)], i32),
+        "bvh_scene_intersect": ([vp, vp, u32, vp, i32], i32),
+        "bvh_scene_tlas": ([vp, C.POINTER(Result)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -258,6 +273,7 @@ class Context:
             _check(lib().bvh_ctx_create(device, C.byref(h)), "bvh_ctx_create")
         self.handle = h
         self.device = device
+        self._scenes = weakref.WeakSet()                  # bvh_scene objects bound to this ctx: destroyed before it
 
     def set_profiling(self, level) -> None:
         """0 off, 1 stage events (reference Timer tokens), 2 + per-kernel events"""
@@ -323,6 +339,8 @@ class Context:
 
     def close(self) -> None:
         if self.handle:
+            for sc in list(self._scenes):
+                sc.close()
             lib().bvh_ctx_destroy(self.handle)
             self.handle = None
 
@@ -371,6 +389,26 @@ class _Builder:
         inp = BuildInput(tri_format, morton_bits, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
                          _ptr(indices) if indices is not None else None, n_vertices, 0)
         _check(lib().bvh_build_ex(context.handle, self.ALGO, C.byref(inp), n, C.byref(self.result), C.byref(self.timings)), f"{ALGO_NAMES[self.ALGO]}::build_ex")
+        return self._publish()
+
+    def build_boxes(self, context: Context, boxes, n: int | None = None, morton_bits: int = 30) -> "_Builder":
+        """bvh_build_boxes: a tree over caller-supplied boxes — a host AABB array (copied to the device for the call) or a device buffer / int address with
+        ``n``.  The result has no triangles (d_tris NULL): intersect / refit need explicit ones."""
+        own = None
+        if isinstance(boxes, np.ndarray):
+            if boxes.dtype != AABB:
+                raise BvhError("boxes must have dtype AABB (24-byte records)")
+            n = boxes.shape[0]
+            own = boxes = context.upload(np.ascontiguousarray(boxes))
+        elif n is None:
+            raise BvhError("n is required for device boxes")
+        self._ctx = context
+        try:
+            _check(lib().bvh_build_boxes(context.handle, self.ALGO, _ptr(boxes), n, int(morton_bits), C.byref(self.result), C.byref(self.timings)),
+                   f"{ALGO_NAMES[self.ALGO]}::build_boxes")
+        finally:
+            if own is not None:
+                own.free()                                # (hipFree waits for the build that read it)
         return self._publish()
 
     def refit(self, primitives, on_device: bool = False, n: int | None = None) -> "_Builder":
@@ -627,3 +665,99 @@ def checksum_host(nodes: np.ndarray, leaves, root: int) -> int:
 
 
 BUILDERS = {ALGO_TWOPASS: TwoPassLbvh, ALGO_SINGLEPASS: SinglePassLbvh, ALGO_PLOCPP: PLOCNew, ALGO_HPLOC: HPLOC}
+
+
+def _as_blas(b):
+    """a Blas (the caller orders its writes before the scene's reads), a built _Builder (its tree's d_tris as Triangle[n]) or a (built _Builder, BuildInput)
+    pair -> (Blas, the builder's Context or None)"""
+    if isinstance(b, Blas):
+        return b, None
+    tris = None
+    if isinstance(b, tuple):
+        b, tris = b
+    if not isinstance(b, _Builder) or b._ctx is None:
+        raise BvhError("a BLAS is a Blas, a built builder or (built builder, BuildInput)")
+    return Blas(Result.from_buffer_copy(b.result), tris if tris is not None else BuildInput(TRI_PADDED64, 30, None, None, None, 0, 0)), b._ctx
+
+
+class Scene:
+    """bvh_scene: instances of bottom-level trees under a top-level tree, bound to one Context (see include/bvh_mi355x.h for the contract).
+    BLASes must not live in this context's arena: build them on other contexts."""
+
+    def __init__(self, ctx: Context):
+        h = C.c_void_p()
+        _check(lib().bvh_scene_create(ctx.handle, C.byref(h)), "bvh_scene_create")
+        self.ctx, self.handle, self.timings, self.n_instances = ctx, h, Timings(), 0
+        ctx._scenes.add(self)
+
+    def build(self, algo: int, blas, instances) -> "Scene":
+        """blas: list of Blas / built builders / (builder, BuildInput); instances: host INSTANCE array, or (device buffer / address, count)"""
+        pairs = [_as_blas(b) for b in blas]
+        arr = (Blas * len(pairs))(*[d for d, _ in pairs])
+        # the builders' contexts: their builds / refits run on other streams, which nothing orders before the scene's reads (include/bvh_mi355x.h)
+        self._blas_ctxs = list({id(c): c for _, c in pairs if c is not None}.values())
+        self._sync_blas()
+        ptr, n, dev = self._instances(instances)
+        _check(lib().bvh_scene_build(self.handle, int(algo), arr, len(pairs), ptr, n, dev, C.byref(self.timings)), "bvh_scene_build")
+        self.n_instances = n
+        return self
+
+    def update(self, instances) -> "Scene":
+        ptr, n, dev = self._instances(instances)
+        if n != self.n_instances:
+            raise BvhError(f"update with {n} instances of a scene built with {self.n_instances}")
+        self._sync_blas()                                 # (a BLAS refit since the build must be complete: update re-reads the root boxes)
+        _check(lib().bvh_scene_update(self.handle, ptr, dev, C.byref(self.timings)), "bvh_scene_update")
+        return self
+
+    def _sync_blas(self) -> None:
+        for c in getattr(self, "_blas_ctxs", ()):
+            if c.handle:
+                c.synchronize()
+
+    def _instances(self, instances):
+        if isinstance(instances, np.ndarray):
+            if instances.dtype != INSTANCE:
+                raise BvhError("instances must have dtype INSTANCE (64-byte records)")
+            self._host = np.ascontiguousarray(instances)
+            return self._host.ctypes.data, len(self._host), 0
+        buf, n = instances
+        return _ptr(buf), int(n), 1
+
+    def intersect(self, rays, query="closest", n_rays: int | None = None) -> np.ndarray:
+        """bvh_scene_intersect: host RAY array or device buffer (+ n_rays) -> host INSTANCE_HIT array"""
+        q = _QUERY_IDS[query] if isinstance(query, str) else int(query)
+        own = None
+        if isinstance(rays, np.ndarray):
+            if rays.dtype != RAY:
+                raise BvhError("rays must have dtype RAY (32-byte records)")
+            n_rays = rays.shape[0]
+            own = rays = self.ctx.upload(np.ascontiguousarray(rays)) if n_rays else None
+        elif n_rays is None:
+            raise BvhError("n_rays is required for device rays")
+        hits = self.ctx.alloc(max(n_rays, 1) * INSTANCE_HIT.itemsize)
+        self._sync_blas()
+        try:
+            _check(lib().bvh_scene_intersect(self.handle, _ptr(rays) if rays is not None else None, n_rays, hits.ptr, q), "bvh_scene_intersect")
+            return hits.download(INSTANCE_HIT, n_rays)
+        finally:
+            hits.free()
+            if own is not None:
+                own.free()
+
+    def tlas(self) -> Result:
+        r = Result()
+        _check(lib().bvh_scene_tlas(self.handle, C.byref(r)), "bvh_scene_tlas")
+        return r
+
+    def close(self) -> None:
+        if self.handle:
+            if self.ctx.handle:                           # (a closed ctx has already destroyed its scenes: Context.close)
+                lib().bvh_scene_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

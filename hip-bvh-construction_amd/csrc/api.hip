@@ -87,6 +87,23 @@ struct bvh_ctx {
     uint32_t plan_n = 0, plan_root = 0;
 };
 
+// bvh_scene: device memory of its own (one allocation, carved as below), outside the ctx's arena; only the top-level build uses the arena
+struct bvh_scene {
+    bvh_ctx* ctx = nullptr;
+    char* mem = nullptr;
+    bool built = false;
+    uint32_t n_blas = 0, n_inst = 0, troot = 0, tlayout = 0;
+    bvh::SceneBlas* blas = nullptr;    // [n_blas] device copies of the validated descriptors
+    bvh_instance* inst_in = nullptr;   // [n_inst] the caller's instance records
+    bvh::SceneInst* inst = nullptr;    // [n_inst] world-to-object + active flag (k_instance_boxes)
+    bvh_aabb* wbox = nullptr;          // [n_inst] world boxes by instance index (the top-level tree's primitive boxes)
+    bvh2_node* tnodes = nullptr;       // top-level tree: layout 0 2n-1 nodes, layout 1 n-1 nodes + n leaves (n_inst >= 2)
+    bvh_primref* tleaves = nullptr;
+    u32* tparent = nullptr;            // [2n-1] top-level plan
+    u32* flags = nullptr;              // [n] refit exchange words (all-INVALID, kept so)
+    u32* overflow = nullptr;           // [1] rays left to the stackless pass
+};
+
 namespace {
 
 // HPLOC: one asynchronous launch below this size, LDS-tiled block kernel + external climb above (measured on MI355X: 1122 vs 966
@@ -368,7 +385,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); warm_optimize(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); warm_optimize(); warm_scene(); }); }
     *out = c;
     return 0;
 }
@@ -542,7 +559,8 @@ int bvh_emit_hploc(bvh_ctx* c, const void* d_prim_aabbs, const uint32_t* d_sorte
 #ifndef SORT_GATE_TOP
 #define SORT_GATE_TOP 1      // 0: the build sorts all 32 key bits at every size (no narrow top pass, no gate)
 #endif
-static int build_impl(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_t n, bvh_result* out, bvh_timings* tm) {
+// d_in_boxes: bvh_build_boxes' input (bvh_aabb[n], device) — stage E copies those boxes instead of reading `in`'s triangles (in->morton_bits still applies)
+static int build_impl(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_t n, bvh_result* out, bvh_timings* tm, const void* d_in_boxes = nullptr) {
     const int key_bits = in->morton_bits == 60 ? 64 : 32;
     hipStream_t s = c->stream;
     const bool sampled = (c->build_counter++ % c->sample_every) == 0u;      // bvh_ctx_set_kernel_sampling: events in every n-th build only
@@ -565,7 +583,7 @@ static int build_impl(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint
     // below the wide sort tiles' threshold (262 144: 0.1141 -> 0.1165 ms), where the build therefore simply sorts all 32 bits like the reference.
     const int end_bit = key_bits == 64 ? 64 : (n >= SORT_WIDE_MIN_N && SORT_GATE_TOP != 0) ? 30 : 32;
     const int passes = sort_passes(0, end_bit);
-    r = stage_extents_valid(in); if (r) return r;
+    if (!d_in_boxes) { r = stage_extents_valid(in); if (r) return r; }
     // what a build needs cleared (digit histograms, look-back status rows and tile tickets of `passes` sort passes, the emitters' queue heads) is cleared by
     // stage E's kernel itself; the scene extent of THIS build was reset by the previous build's Morton kernel (two extents, used alternately) — explicitly
     // only for a context's first build, after a re-allocation or after a build that failed half-way
@@ -578,7 +596,8 @@ static int build_impl(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint
     if (algo == BVH_PLOCPP) ploc_begin_prep(c->ploc, n, prep);       // (the stage entry point bvh_emit_ploc launches k_ploc_init instead)
     const bool explicit_reset = !c->scene_ready;
     c->scene_ready = false;
-    r = stage_extents_fmt(s, in, n, c->boxes, scene, explicit_reset, &prep); if (r) return r;
+    if (d_in_boxes) launch_extents_boxes(s, d_in_boxes, n, c->boxes, scene, explicit_reset, &prep);
+    else { r = stage_extents_fmt(s, in, n, c->boxes, scene, explicit_reset, &prep); if (r) return r; }
     if (prof) HIP_TRY(hipEventRecord(c->ev[1], s));
     // M: CalculateMortonCodes (token CalculateMortonCodesTime); values are implicit (value i = i), produced by sort pass 0
     if (key_bits == 64) launch_morton64(s, c->boxes, n, scene, reinterpret_cast<u64*>(c->keys), 60, c->sort.hist, passes, scene_next);
@@ -595,7 +614,7 @@ static int build_impl(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint
         case BVH_LBVH_SINGLEPASS: launch_lbvh_single(s, c->boxes, c->skeys, key_bits, c->svals, n, c->nodes, c->hploc.dep, c->small, c->ploc.list0, c->lbvh_queue_capacity, c->hploc.queue_count, true, (int)c->options[BVH_OPT_LBVH_SCHEDULER]); break;
         case BVH_LBVH_TWOPASS:    launch_lbvh_two(s, c->boxes, c->skeys, key_bits, c->svals, n, c->nodes, c->parent, c->flags, c->hploc.dep, c->small,
                                                   c->ploc.list0, c->lbvh_queue_capacity, c->hploc.queue_count, true, (int)c->options[BVH_OPT_LBVH_SCHEDULER]); break;
-        case BVH_HPLOC:           c->hploc.leaf_tris = (LEAF_FROM_TRIS && in->tri_format == BVH_TRI_PADDED64) ? in->d_tris : nullptr;
+        case BVH_HPLOC:           c->hploc.leaf_tris = (LEAF_FROM_TRIS && !d_in_boxes && in->tri_format == BVH_TRI_PADDED64) ? in->d_tris : nullptr;
                                   emit_hploc(c, s, c->boxes, c->skeys, key_bits, c->svals, n, c->nodes, c->leaves, true);
                                   c->hploc.leaf_tris = nullptr;
                                   out->d_leaves = c->leaves; out->layout = 1; break;
@@ -614,7 +633,7 @@ static int build_impl(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint
     out->d_nodes = c->nodes; out->d_prim_aabbs = c->boxes; out->d_scene_extent = scene;
     out->d_sorted_keys = c->skeys; out->d_sorted_vals = c->svals;
     out->n_internal = n - 1; out->n_leaves = n; out->key_bits = (uint32_t)key_bits; out->reserved = 0;
-    out->d_tris = in->tri_format == BVH_TRI_INDEXED ? in->d_vertices : in->d_tris; out->d_morton_keys = c->keys;
+    out->d_tris = d_in_boxes ? nullptr : in->tri_format == BVH_TRI_INDEXED ? in->d_vertices : in->d_tris; out->d_morton_keys = c->keys;
     if (tm) {
         std::memset(tm, 0, sizeof *tm);
         tm->bytes_algorithmic = algorithmic_bytes(algo, n);
@@ -654,6 +673,17 @@ int bvh_build_ex(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_t 
     Bind b(c->device);
     int r = ensure_capacity(c, n); if (r) return r;
     return build_impl(c, algo, in, n, out, tm);
+}
+
+int bvh_build_boxes(bvh_ctx* c, bvh_algo algo, const void* d_boxes, uint32_t n, int morton_bits, bvh_result* out, bvh_timings* tm) {
+    if (!c || !d_boxes || !out || n < 2 || (int)algo < 0 || (int)algo > 3) return BVH_E_INVALID_ARG;
+    if (morton_bits != 30 && morton_bits != 60) return BVH_E_INVALID_ARG;
+    if (n >= (1u << 30)) return BVH_E_TOO_LARGE;
+    Bind b(c->device);
+    int r = ensure_capacity(c, n); if (r) return r;
+    bvh_build_input in; std::memset(&in, 0, sizeof in);
+    in.tri_format = BVH_TRI_PADDED64; in.morton_bits = (uint32_t)morton_bits;
+    return build_impl(c, algo, &in, n, out, tm, d_boxes);
 }
 
 // ---- refit (no counterpart in the reference) ----------------------------------------------------------------------------------------------------
@@ -797,6 +827,167 @@ int bvh_optimize(bvh_ctx* c, bvh_result* io, uint32_t rounds, bvh_timings* tm) {
             tm->ms_total = tm->ms_build;
         }
     }
+    return 0;
+}
+
+// ---- instanced scenes (no counterpart in the reference) -----------------------------------------------------------------------------------------
+int bvh_scene_create(bvh_ctx* c, bvh_scene** out) {
+    if (!c || !out) return BVH_E_INVALID_ARG;
+    bvh_scene* sc = new (std::nothrow) bvh_scene();
+    if (!sc) return BVH_E_INTERNAL;
+    sc->ctx = c;
+    *out = sc;
+    return 0;
+}
+
+void bvh_scene_destroy(bvh_scene* sc) {
+    if (!sc) return;
+    if (sc->mem) { Bind b(sc->ctx->device); hipStreamSynchronize(sc->ctx->stream); hipFree(sc->mem); }
+    delete sc;
+}
+
+namespace {
+inline bool ranges_overlap(const void* p, uint64_t bytes, const void* q, uint64_t qbytes) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && bytes && qbytes && a < b + qbytes && b < a + bytes;
+}
+// one bvh_blas -> its device descriptor; BVH_E_INVALID_ARG for what bvh_intersect would reject and for arrays inside the ctx's arena / triangle staging buffer
+int blas_descriptor(const bvh_ctx* c, const bvh_blas& in, SceneBlas& d) {
+    const bvh_result& t = in.tree;
+    const uint32_t n = t.n_leaves;
+    if (n < 2 || n >= (1u << 30) || t.layout > 1u || !t.d_nodes || (t.layout == 1u && !t.d_leaves) || t.root >= n - 1) return BVH_E_INVALID_ARG;
+    bvh_build_input tri = in.tris;
+    if (tri.tri_format == BVH_TRI_PADDED64 && !tri.d_tris) tri.d_tris = t.d_tris;
+    if (stage_extents_valid(&tri)) return BVH_E_INVALID_ARG;
+    const uint64_t node_bytes = (uint64_t)(t.layout == 0 ? 2ull * n - 1 : n - 1ull) * sizeof(bvh2_node), leaf_bytes = t.layout == 1 ? (uint64_t)n * sizeof(bvh_primref) : 0;
+    const void* arrays[4] = { t.d_nodes, t.layout == 1 ? t.d_leaves : nullptr, nullptr, nullptr };
+    uint64_t sizes[4] = { node_bytes, leaf_bytes, 0, 0 };
+    switch (tri.tri_format) {
+        case BVH_TRI_PADDED64: arrays[2] = tri.d_tris; sizes[2] = (uint64_t)n * 64; break;
+        case BVH_TRI_PACKED36: arrays[2] = tri.d_tris; sizes[2] = (uint64_t)n * 36; break;
+        default: arrays[2] = tri.d_vertices; sizes[2] = (uint64_t)tri.n_vertices * 12; arrays[3] = tri.d_indices; sizes[3] = (uint64_t)n * 12; break;
+    }
+    for (int k = 0; k < 4; ++k)
+        if (ranges_overlap(arrays[k], sizes[k], c->arena, c->arena_bytes) || ranges_overlap(arrays[k], sizes[k], c->tris, (uint64_t)c->tris_cap * sizeof(bvh_triangle)))
+            return BVH_E_INVALID_ARG;
+    std::memset(&d, 0, sizeof d);
+    d.nodes = t.d_nodes; d.leaves = t.layout == 1 ? t.d_leaves : nullptr; d.tris = tri.tri_format == BVH_TRI_INDEXED ? tri.d_vertices : tri.d_tris;
+    d.idx = tri.tri_format == BVH_TRI_INDEXED ? tri.d_indices : nullptr;
+    d.n = n; d.root = t.root; d.layout = t.layout; d.fmt = tri.tri_format; d.nv = tri.n_vertices;
+    return 0;
+}
+// instance records -> the scene's copy (host or device source), then k_instance_boxes
+int scene_instances(bvh_scene* sc, const bvh_instance* instances, int on_device) {
+    hipStream_t s = sc->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(sc->inst_in, instances, (size_t)sc->n_inst * sizeof(bvh_instance), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    if (!on_device) HIP_TRY(hipStreamSynchronize(s));        // (host records: read before the call returns)
+    launch_instance_boxes(s, sc->inst_in, sc->n_inst, sc->blas, sc->n_blas, sc->inst, sc->wbox);
+    return herr(hipGetLastError());
+}
+} // namespace
+
+int bvh_scene_build(bvh_scene* sc, bvh_algo algo, const bvh_blas* blas, uint32_t n_blas, const bvh_instance* instances, uint32_t n_inst, int on_device,
+                    bvh_timings* tm) {
+    if (!sc || !blas || !instances || n_blas == 0 || n_inst == 0 || (int)algo < 0 || (int)algo > 3) return BVH_E_INVALID_ARG;
+    if (n_inst >= (1u << 30)) return BVH_E_TOO_LARGE;
+    bvh_ctx* c = sc->ctx;
+    std::vector<SceneBlas> desc(n_blas);
+    uint64_t plan_words = 0;
+    for (uint32_t k = 0; k < n_blas; ++k) {
+        const int r = blas_descriptor(c, blas[k], desc[k]); if (r) return r;
+        plan_words += 2ull * desc[k].n - 1;
+    }
+    Bind b(c->device);
+    if (tm) std::memset(tm, 0, sizeof *tm);
+    // carve the scene's memory (freed and re-made on every build: the BLAS set and the instance count may change)
+    const size_t n = n_inst;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
+    const size_t o_blas = take(n_blas * sizeof(SceneBlas)), o_in = take(n * sizeof(bvh_instance)), o_inst = take(n * sizeof(SceneInst)), o_wbox = take(n * sizeof(bvh_aabb));
+    const size_t o_tnodes = take((2 * n - 1) * sizeof(bvh2_node)), o_tleaves = take(n * sizeof(bvh_primref)), o_tparent = take((2 * n - 1) * sizeof(u32));
+    const size_t o_flags = take(n * sizeof(u32)), o_over = take(sizeof(u32)), o_plans = take(plan_words * sizeof(u32));
+    sc->built = false;
+    if (sc->mem) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(sc->mem)); sc->mem = nullptr; }
+    HIP_TRY(hipMalloc(&sc->mem, off));
+    char* m = sc->mem;
+    sc->blas = reinterpret_cast<SceneBlas*>(m + o_blas); sc->inst_in = reinterpret_cast<bvh_instance*>(m + o_in); sc->inst = reinterpret_cast<SceneInst*>(m + o_inst);
+    sc->wbox = reinterpret_cast<bvh_aabb*>(m + o_wbox); sc->tnodes = reinterpret_cast<bvh2_node*>(m + o_tnodes); sc->tleaves = reinterpret_cast<bvh_primref*>(m + o_tleaves);
+    sc->tparent = reinterpret_cast<u32*>(m + o_tparent); sc->flags = reinterpret_cast<u32*>(m + o_flags); sc->overflow = reinterpret_cast<u32*>(m + o_over);
+    sc->n_blas = n_blas; sc->n_inst = n_inst;
+    hipStream_t s = c->stream;
+    // the descriptors (each with its slot of the plans), copied before anything is enqueued: a blocking copy, so that an early return cannot leave a copy
+    // from `desc` queued; then every BLAS's parent plan (the stackless pass)
+    u32* const plans = reinterpret_cast<u32*>(m + o_plans);
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < n_blas; ++k) { desc[k].parent = plans + at; at += 2ull * desc[k].n - 1; }
+    HIP_TRY(hipMemcpy(sc->blas, desc.data(), n_blas * sizeof(SceneBlas), hipMemcpyHostToDevice));
+    for (uint32_t k = 0; k < n_blas; ++k) launch_refit_plan(s, desc[k].nodes, desc[k].n, desc[k].root, const_cast<u32*>(desc[k].parent));
+    HIP_TRY(hipMemsetAsync(sc->flags, 0xFF, n * sizeof(u32), s));
+    int r = scene_instances(sc, instances, on_device); if (r) return r;
+    sc->troot = 0; sc->tlayout = (algo == BVH_PLOCPP || algo == BVH_HPLOC) ? 1u : 0u;
+    if (n_inst >= 2) {
+        // the top-level tree: built in the ctx's arena over the world boxes, copied out, and its own plan
+        bvh_result t;
+        r = bvh_build_boxes(c, algo, sc->wbox, n_inst, 30, &t, tm); if (r) return r;
+        sc->troot = t.root; sc->tlayout = t.layout;
+        HIP_TRY(hipMemcpyAsync(sc->tnodes, t.d_nodes, (t.layout == 0 ? 2 * n - 1 : n - 1) * sizeof(bvh2_node), hipMemcpyDeviceToDevice, s));
+        if (t.layout == 1) HIP_TRY(hipMemcpyAsync(sc->tleaves, t.d_leaves, n * sizeof(bvh_primref), hipMemcpyDeviceToDevice, s));
+        launch_refit_plan(s, sc->tnodes, n_inst, sc->troot, sc->tparent);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));                          // (bvh_scene_build is blocking: errors of the enqueued work surface here)
+    sc->built = true;
+    return 0;
+}
+
+int bvh_scene_update(bvh_scene* sc, const bvh_instance* instances, int on_device, bvh_timings* tm) {
+    if (!sc || !instances || !sc->built) return BVH_E_INVALID_ARG;
+    bvh_ctx* c = sc->ctx;
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    const bool prof = c->profiling;
+    if (prof) HIP_TRY(hipEventRecord(c->ev[0], s));
+    int r = scene_instances(sc, instances, on_device); if (r) return r;
+    if (sc->n_inst >= 2) launch_refit_climb(s, sc->wbox, sc->tnodes, sc->tleaves, (int)sc->tlayout, sc->n_inst, sc->tparent, sc->flags);
+    HIP_TRY(hipGetLastError());
+    if (prof) HIP_TRY(hipEventRecord(c->ev[4], s));
+    if (tm) {
+        std::memset(tm, 0, sizeof *tm);
+        tm->sampled = prof ? 1u : 0u;
+        if (prof) { HIP_TRY(hipEventSynchronize(c->ev[4])); HIP_TRY(hipEventElapsedTime(&tm->ms_build, c->ev[0], c->ev[4])); tm->ms_total = tm->ms_build; }
+    }
+    return 0;
+}
+
+int bvh_scene_intersect(bvh_scene* sc, const bvh_ray* d_rays, uint32_t n_rays, bvh_instance_hit* d_hits, int query) {
+    if (!sc || !d_rays || !d_hits || !sc->built) return BVH_E_INVALID_ARG;
+    if (query != BVH_QUERY_CLOSEST && query != BVH_QUERY_ANY) return BVH_E_INVALID_ARG;
+    const uintptr_t r0 = (uintptr_t)d_rays, r1 = r0 + (uint64_t)n_rays * sizeof(bvh_ray), h0 = (uintptr_t)d_hits, h1 = h0 + (uint64_t)n_rays * sizeof(bvh_instance_hit);
+    if (n_rays && r0 < h1 && h0 < r1) return BVH_E_INVALID_ARG;
+    if (n_rays == 0) return 0;
+    bvh_ctx* c = sc->ctx;
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    HIP_TRY(hipMemsetAsync(sc->overflow, 0, sizeof(u32), s));
+    SceneQuery q;
+    q.rays = d_rays; q.hits = d_hits; q.overflow = sc->overflow;
+    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
+    q.n_rays = n_rays; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout;
+    launch_scene_intersect(s, query, q);
+    HIP_TRY(hipGetLastError());
+    if (install.on) c->recorder.mark(s, nullptr);
+    return 0;
+}
+
+int bvh_scene_tlas(const bvh_scene* sc, bvh_result* out) {
+    if (!sc || !out || !sc->built) return BVH_E_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    const uint32_t n = sc->n_inst;
+    out->n_leaves = n; out->n_internal = n - 1; out->root = sc->troot; out->layout = sc->tlayout; out->key_bits = 32;
+    out->d_prim_aabbs = sc->wbox;
+    if (n >= 2) { out->d_nodes = sc->tnodes; out->d_leaves = sc->tlayout == 1 ? sc->tleaves : nullptr; }
     return 0;
 }
 

@@ -36,6 +36,8 @@ constexpr int SORT_COUNTER_CLEAR = 8;       // = SORT_MAX_PASSES tile tickets
 void launch_extents(hipStream_t s, const void* d_tris, uint32_t n, void* d_boxes, void* d_scene, bool reset_scene = true, const PrepArgs* prep = nullptr);
 void launch_extents_packed(hipStream_t s, const void* d_tris36, uint32_t n, void* d_boxes, void* d_scene, bool reset_scene = true, const PrepArgs* prep = nullptr);
 void launch_extents_indexed(hipStream_t s, const void* d_vertices, const void* d_indices, uint32_t n_vertices, uint32_t n, void* d_boxes, void* d_scene, bool reset_scene = true, const PrepArgs* prep = nullptr);
+// bvh_build_boxes' stage E: bvh_aabb[n] (device; may be d_boxes itself) copied into d_boxes and unioned into d_scene
+void launch_extents_boxes(hipStream_t s, const void* d_in, uint32_t n, void* d_boxes, void* d_scene, bool reset_scene = true, const PrepArgs* prep = nullptr);
 void launch_morton(hipStream_t s, const void* d_boxes, uint32_t n, const void* d_scene, uint32_t* d_keys, uint32_t* d_vals,
                    uint32_t* d_hist /*may be null*/, int hist_bits, int passes, float* d_reset_next = nullptr /* Aabb::reset of another extent (the next build's) */);
 // extended Morton code with a 60-bit budget in u64 keys (total_bits = 30 reproduces launch_morton's codes: the parity pin)
@@ -160,6 +162,24 @@ void launch_intersect(hipStream_t s, int layout, int query, int tri_format, cons
                       const void* d_rays, uint32_t n_rays, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root, void* d_hits,
                       uint32_t* d_overflow, const uint32_t* d_parent);
 
+// ---- instanced scenes (scene.hip): bvh_scene's kernels.  SceneBlas: the device copy of one validated bvh_blas (64 bytes, read whole when a ray enters an
+// instance); tris = Triangle[n] / float[9n] / the vertices of INDEXED input, idx = INDEXED indices, parent = the BLAS's k_refit_plan plan (u32[2n-1]).
+struct SceneBlas { const void* nodes; const void* leaves; const void* tris; const void* idx; const uint32_t* parent; uint32_t n, root, layout, fmt, nv, pad; };
+static_assert(sizeof(SceneBlas) == 64, "SceneBlas is one 64-byte record");
+// per instance, written by k_instance_boxes: world-to-object 3x4 (row-major, f32) and the BLAS index (BVH_INVALID: inactive, never entered)
+struct SceneInst { float w2o[12]; uint32_t blas, pad[3]; };
+static_assert(sizeof(SceneInst) == 64, "SceneInst is one 64-byte record");
+struct SceneQuery {
+    const void* rays; void* hits; uint32_t* overflow;           // bvh_ray[n_rays], bvh_instance_hit[n_rays], one word zeroed before the launch
+    const void* tnodes; const void* tleaves; const uint32_t* tparent;   // top-level tree (n_inst >= 2) and its plan
+    const SceneInst* inst; const SceneBlas* blas; const void* wbox;      // SceneInst[n_inst], SceneBlas[n_blas], bvh_aabb[n_inst]
+    uint32_t n_rays, n_inst, troot, tlayout;
+};
+// one thread per instance: inverse, active flag and world box from d_instances (bvh_instance[n_inst]) and the BLASes' root boxes
+void launch_instance_boxes(hipStream_t s, const void* d_instances, uint32_t n_inst, const SceneBlas* d_blas, uint32_t n_blas, SceneInst* d_inst, void* d_wbox);
+// k_scene_intersect (short stack shared by both levels) + k_scene_intersect_deep (stackless, returns at once while *overflow == 0)
+void launch_scene_intersect(hipStream_t s, int query, const SceneQuery& q);
+
 // ---- BVH2 -> BVH4 collapse (collapse.hip)
 constexpr int COLLAPSE_MAX_BATCH = 64;                       // levels per batch of launches (one counter word per level)
 constexpr int COLLAPSE_STATE_WORDS = COLLAPSE_MAX_BATCH;
@@ -188,6 +208,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query(); void warm_optimize();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query(); void warm_optimize(); void warm_scene();
 
 } // namespace bvh

@@ -137,6 +137,20 @@ __global__ __launch_bounds__(EX_BLOCK) void k_extents_indexed(const float* __res
     block_reduce_scene(acc, scene);
 }
 
+// Box input (bvh_build_boxes): the caller's boxes are copied into the build's box array and unioned into the scene extent — the same grid, loop and
+// reduction as k_extents, so boxes that k_extents wrote for some triangles give the same extent bits.  in may alias boxes (same element, same thread).
+__global__ __launch_bounds__(EX_BLOCK) void k_extents_boxes(const bvh_aabb* in, bvh_aabb* boxes, float* __restrict__ scene, u32 n, PrepArgs prep) {
+    prep_slice(prep);
+    Box acc = box_empty();
+    const u32 stride = gridDim.x * EX_BLOCK;
+    for (u32 i = blockIdx.x * EX_BLOCK + threadIdx.x; i < n; i += stride) {
+        const Box bx = box_load(in + i);
+        box_store(boxes + i, bx);
+        acc = box_union(acc, bx);
+    }
+    block_reduce_scene(acc, scene);
+}
+
 __global__ void k_reset_scene(float* scene) {   // Aabb::reset on d_sceneExtents (src/PLOC++Bvh.cpp:23-25)
     if (threadIdx.x < 3) scene[threadIdx.x] = FMAX; else if (threadIdx.x < 6) scene[threadIdx.x] = -FMAX;
 }
@@ -399,6 +413,12 @@ void launch_extents_indexed(hipStream_t s, const void* d_vertices, const void* d
     hipLaunchKernelGGL(k_extents_indexed, dim3(ex_grid(n)), dim3(EX_BLOCK), 0, s, (const float*)d_vertices, (const u32*)d_indices, n_vertices, (bvh_aabb*)d_boxes, (float*)d_scene, n, pa);
 }
 
+void launch_extents_boxes(hipStream_t s, const void* d_in, u32 n, void* d_boxes, void* d_scene, bool reset_scene, const PrepArgs* prep) {
+    const PrepArgs pa = prep ? *prep : PrepArgs{};
+    if (reset_scene) hipLaunchKernelGGL(k_reset_scene, dim3(1), dim3(64), 0, s, (float*)d_scene);
+    KernelScope ks(s, "k_extents_boxes");
+    hipLaunchKernelGGL(k_extents_boxes, dim3(ex_grid(n)), dim3(EX_BLOCK), 0, s, (const bvh_aabb*)d_in, (bvh_aabb*)d_boxes, (float*)d_scene, n, pa);
+}
 // the per-scene plan of the Morton kernels, as the device evaluates it (bvh_stage_morton_plan): {axis[3], bits[3], pre[2], pre_sum, swap}
 __global__ void k_morton_plan(const float* __restrict__ scene, int* __restrict__ out, u32 total_bits) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;

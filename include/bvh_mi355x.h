@@ -142,6 +142,13 @@ typedef struct {
     uint32_t    reserved;
 } bvh_build_input;
 int  bvh_build_ex(bvh_ctx* ctx, bvh_algo algo, const bvh_build_input* in, uint32_t n, bvh_result* out, bvh_timings* timings /* may be NULL */);
+/* Build over caller-supplied boxes instead of triangles (procedural primitives, particles; bvh_scene's top-level tree).  d_boxes: bvh_aabb[n] on the device, read
+ * once (it may be the ctx's own d_prim_aabbs).  The pipeline of bvh_build_ex with only stage E replaced: the boxes are copied into the ctx's box array and unioned
+ * into the scene extent.  Contract: given the boxes stage E writes for some triangles (a result's d_prim_aabbs), the tree is byte-identical to the one bvh_build_ex
+ * builds from those triangles with the same algo and morton_bits (nodes, leaves, root, d_sorted_keys, d_sorted_vals), for every builder and scheduler option.
+ * In the result d_tris is NULL: bvh_intersect / bvh_refit of it need an explicit `tris`.  Errors: those of bvh_build_ex (morton_bits 30 or 60), NULL d_boxes. */
+int  bvh_build_boxes(bvh_ctx* ctx, bvh_algo algo, const void* d_boxes /* bvh_aabb[n], device */, uint32_t n, int morton_bits /* 30 or 60 */,
+                     bvh_result* out, bvh_timings* timings /* may be NULL */);
 /* stage E on any input format */
 int  bvh_stage_extents_ex(bvh_ctx* ctx, const bvh_build_input* in, uint32_t n, void* d_prim_aabbs, void* d_scene_extent);
 /* stage M with a total_bits budget (3..60) into u64 keys; total_bits = 30 reproduces bvh_stage_morton's codes.  The codes keep the reference's
@@ -234,6 +241,62 @@ int  bvh_intersect(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* 
  * node, rounds outside [1, 8]: BVH_E_INVALID_ARG.  n_leaves larger than the ctx's capacity: BVH_E_INVALID_ARG — an optimise never re-allocates the arena (io
  * may point into it); call bvh_ctx_reserve first.  Asynchronous on the ctx's stream, except for what the timings need. */
 int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* timings /* may be NULL */);
+
+/* ---- instanced scenes (two levels; no counterpart in the reference beyond one Transformation, src/Common.h:541-548) ------------------------------------
+ * A scene places bottom-level trees (BLASes) by 3x4 transforms (bvh_instance) under a top-level tree over the instances' world boxes, and answers ray queries
+ * against all of them: the same mesh placed many times is stored once, and moving an instance costs a refit of the top-level tree, not a rebuild.
+ * Bottom level: bvh_blas = a tree (any bvh_result bvh_intersect accepts, either layout) + its triangles (any bvh_tri_format; tri_format PADDED64 with d_tris
+ * NULL reads tree.d_tris as Triangle[n_leaves]).  Arrays are REFERENCED, not copied: they must stay valid and keep their topology while the scene is used.
+ * Ordering: the scene reads a BLAS's arrays on ITS ctx's stream (bvh_scene_build: the plan and the root box; bvh_scene_update: the root box; queries: everything),
+ * and nothing orders those reads after work enqueued on other streams.  All work that writes a BLAS's arrays (its build, bvh_refit, bvh_optimize, copies) must
+ * be complete before bvh_scene_build, bvh_scene_update and bvh_scene_intersect are called — e.g. bvh_ctx_synchronize on the ctx that built or refit it.
+ * Ownership: a scene is bound to one ctx and enqueues on its stream.  It owns device memory (outside the ctx's arena) for the BLAS table (device copies of the
+ * descriptors), the instance array, the per-instance world-to-object matrices and world boxes, the top-level tree's nodes and leaves, and the parent plans
+ * (k_refit_plan, 4 bytes x (2n-1) per tree, the top level and every BLAS) of the stackless pass: scene queries have no depth limit at either level.  The top-level
+ * tree is built in the ctx's arena with bvh_build_boxes and copied out, so bvh_scene_build counts as a build on the ctx: it invalidates earlier bvh_results that
+ * point into the arena.  Scenes stay valid across later builds on the ctx.  Destroy scenes before their ctx.
+ * A BLAS whose d_nodes, d_leaves or triangle arrays overlap the scene's ctx's arena or its triangle staging buffer (what bvh_build of a host input copies to) is
+ * rejected (BVH_E_INVALID_ARG): the scene build would overwrite it.  Build BLASes on other contexts, keep bvh_batch trees (their triangles uploaded by the caller),
+ * or copy them out with bvh_dev_copy.
+ * Instance maths (f32 unless stated, no contraction; tests/test_scene.py restates it in numpy):
+ *   world_to_object = inverse of M = [A | t]: in f64 from the f32 entries, a_ij = M[4i + j]; cofactors c00 = a11 a22 - a12 a21, c01 = a12 a20 - a10 a22,
+ *     c02 = a10 a21 - a11 a20; det = (a00 c00 + a01 c01) + a02 c02; A^-1 = adj(A) / det with adj row 0 = {c00, a02 a21 - a01 a22, a01 a12 - a02 a11},
+ *     row 1 = {c01, a00 a22 - a02 a20, a02 a10 - a00 a12}, row 2 = {c02, a01 a20 - a00 a21, a00 a11 - a01 a10} (each entry divided by det); translation
+ *     w_i3 = -((A^-1_i0 t0 + A^-1_i1 t1) + A^-1_i2 t2) with the unrounded f64 A^-1; every entry then rounded once to f32.
+ *   object-space ray: o'_i = ((w_i0 ox + w_i1 oy) + w_i2 oz) + w_i3, d'_i = (w_i0 dx + w_i1 dy) + w_i2 dz; tmin / tmax unchanged.  d' is not normalised: t means
+ *     the same in both frames and is compared across instances.
+ *   world box: componentwise fminf / fmaxf over the 8 corners of the BLAS root box (nodes[root].aabb in both layouts; corner k takes max x if k & 1, max y if
+ *     k & 2, max z if k & 4), each mapped by M in the order of o'.
+ *   inactive instance: blas >= n_blas, a non-finite entry of M, det 0 or not finite, or a non-finite rounded inverse entry.  Its world box is the reset box
+ *     {+FLT_MAX, -FLT_MAX}; it is never hit.
+ * n_instances == 1 is supported: there is no top-level tree (bvh_scene_tlas reports n_leaves = 1 and d_nodes = NULL); a query tests the instance's world box
+ * and enters it.  With n_instances >= 2 the top-level tree is built by any algo.
+ * Queries: bvh_intersect's hit test (tri_hit, same acceptance rule) on the object-space ray.  BVH_QUERY_CLOSEST: the accepted hit with the smallest
+ * (t, instance_idx, prim_idx), compared lexicographically — independent of the top-level builder, the BLAS builders, layouts and formats, and traversal order.
+ * BVH_QUERY_ANY: some accepted hit.  Hit = {t, u, v, prim_idx, instance_idx, 0, 0, 0}; miss = {tmax, 0, 0, BVH_INVALID, BVH_INVALID, 0, 0, 0}; NaN rays and rays
+ * with !(tmin < tmax) miss.  Box tests are bvh_intersect's at both levels.  Well-conditioned (answers exact): the object-space ray is
+ * well-conditioned for its BLAS (§8b), and every accepted hit's world point o + t d (f64) lies in its instance's world box grown by half the box test's growth.
+ * Asynchronous on the ctx's stream, no read-back.  bvh_ctx_kernel_times reports k_scene_intersect and k_scene_intersect_deep.
+ * Errors write nothing (BVH_E_INVALID_ARG): bvh_intersect's checks, a NULL or unbuilt scene, overlapping d_rays / d_hits ranges.  n_rays == 0: nothing is touched.
+ * Update: bvh_scene_update takes n_instances records as the build did; every field may change, blas included.  It recomputes the inverses and world boxes from the
+ * BLAS root boxes as they are now (bvh_refit a BLAS, then update: correct) and refits the top-level tree in place (k_refit_climb), topology kept.  A BLAS whose
+ * topology changed (a rebuild, bvh_optimize) needs a new bvh_scene_build: its parent plan is stale.  Asynchronous with device instances; host instances are
+ * read before the call returns.
+ * bvh_scene_build: blas[n_blas] host descriptors (n_blas >= 1), instances[n_instances] (1 <= n_instances < 2^30) on the host or (instances_on_device) the device.
+ * Errors (BVH_E_INVALID_ARG, the scene unchanged): NULL arguments, algo out of range, a BLAS bvh_intersect would reject, a BLAS in the ctx's arena.  A HIP error
+ * after validation leaves the scene unbuilt (queries and updates then return BVH_E_INVALID_ARG until a build succeeds).  timings: the top-level build's
+ * (bvh_build_boxes; all zero with one instance).  Blocking (the descriptors are copied from host memory before any kernel is enqueued).
+ * bvh_scene_tlas: the top-level tree as a bvh_result — layout by algo, d_prim_aabbs = the world boxes by instance index, d_tris / d_scene_extent / d_sorted_* /
+ * d_morton_keys NULL — readable by bvh_sah_cost, bvh_checksum and bvh_download (nodes and leaves).  Valid until the next bvh_scene_build or bvh_scene_destroy. */
+typedef struct { bvh_result tree; bvh_build_input tris; } bvh_blas;   /* tris.tri_format PADDED64 with d_tris NULL: tree.d_tris is Triangle[n_leaves] */
+typedef struct bvh_scene bvh_scene;
+int  bvh_scene_create(bvh_ctx* ctx, bvh_scene** out);
+void bvh_scene_destroy(bvh_scene* scene);
+int  bvh_scene_build(bvh_scene* scene, bvh_algo algo, const bvh_blas* blas /* host [n_blas] */, uint32_t n_blas,
+                     const bvh_instance* instances, uint32_t n_instances, int instances_on_device, bvh_timings* timings /* may be NULL */);
+int  bvh_scene_update(bvh_scene* scene, const bvh_instance* instances, int instances_on_device, bvh_timings* timings /* may be NULL */);
+int  bvh_scene_intersect(bvh_scene* scene, const bvh_ray* d_rays, uint32_t n_rays, bvh_instance_hit* d_hits, int query /* bvh_query_kind */);
+int  bvh_scene_tlas(const bvh_scene* scene, bvh_result* out);
 
 /* ---- stage-level entry points (one per reference kernel / library call on the path) -------------------------- */
 
