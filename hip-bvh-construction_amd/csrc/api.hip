@@ -193,7 +193,7 @@ void carve(bvh_ctx* c, char* base, uint32_t cap, size_t* total) {
     c->ploc.ids1 = k.take<u32>(n);
     c->ploc.status = k.take<u64>((size_t)PLOC_MAX_ITERS * ploc_chunks(cap));
     c->ploc.state = k.take<u32>(PLOC_STATE_WORDS);
-    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's overflow count
+    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's / bvh_closest_point's overflow count
     c->hploc.zero_parent = c->small + 1;
     *total = k.off;
 }
@@ -385,7 +385,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); warm_optimize(); warm_scene(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); }); }
     *out = c;
     return 0;
 }
@@ -755,33 +755,71 @@ int bvh_refit_ex(bvh_ctx* c, bvh_result* io, const bvh_build_input* in, bvh_timi
 }
 
 // ---- ray queries (no counterpart in the reference) ----------------------------------------------------------------------------------------------
-// every argument is checked before anything is enqueued: an error writes nothing.  The arena is never re-allocated (the tree may point into it).
-int bvh_intersect(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_ray* d_rays, uint32_t n_rays, bvh_hit* d_hits, int query) {
-    if (!c || !tree || !d_rays || !d_hits) return BVH_E_INVALID_ARG;
+// the checks bvh_intersect and bvh_closest_point share: every argument is checked before anything is enqueued, so an error writes nothing.  The arena is never
+// re-allocated (the tree may point into it).  in = the validated triangles; d_q / d_h: the query and answer arrays (q_bytes / h_bytes long), which must not overlap
+static int query_check(const bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, int query, const void* d_q, uint64_t q_bytes, const void* d_h,
+                       uint64_t h_bytes, bvh_build_input* in) {
+    if (!c || !tree || !d_q || !d_h) return BVH_E_INVALID_ARG;
     const uint32_t n = tree->n_leaves;
     if (n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1) return BVH_E_INVALID_ARG;
-    bvh_build_input in; std::memset(&in, 0, sizeof in);
-    if (tris) { if (stage_extents_valid(tris)) return BVH_E_INVALID_ARG; in = *tris; }
-    else { if (!tree->d_tris) return BVH_E_INVALID_ARG; in.tri_format = BVH_TRI_PADDED64; in.d_tris = tree->d_tris; }
+    std::memset(in, 0, sizeof *in);
+    if (tris) { if (stage_extents_valid(tris)) return BVH_E_INVALID_ARG; *in = *tris; }
+    else { if (!tree->d_tris) return BVH_E_INVALID_ARG; in->tri_format = BVH_TRI_PADDED64; in->d_tris = tree->d_tris; }
     if (query != BVH_QUERY_CLOSEST && query != BVH_QUERY_ANY) return BVH_E_INVALID_ARG;
-    const uintptr_t r0 = (uintptr_t)d_rays, r1 = r0 + (uint64_t)n_rays * sizeof(bvh_ray), h0 = (uintptr_t)d_hits, h1 = h0 + (uint64_t)n_rays * sizeof(bvh_hit);
-    if (n_rays && r0 < h1 && h0 < r1) return BVH_E_INVALID_ARG;
+    const uintptr_t q0 = (uintptr_t)d_q, q1 = q0 + q_bytes, h0 = (uintptr_t)d_h, h1 = h0 + h_bytes;
+    if (q_bytes && q0 < h1 && h0 < q1) return BVH_E_INVALID_ARG;
     if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
+    return 0;
+}
+
+// the stackless pass's parent plan: bvh_refit's, cached for the ctx's own tree under the same rule
+static void query_plan(bvh_ctx* c, const bvh_result* tree, hipStream_t s) {
+    const bool own = tree->d_nodes == c->nodes;
+    if (!own || c->plan_serial != c->tree_serial || c->plan_n != tree->n_leaves || c->plan_root != tree->root) {
+        launch_refit_plan(s, tree->d_nodes, tree->n_leaves, tree->root, c->parent);
+        c->plan_serial = own ? c->tree_serial : 0; c->plan_n = tree->n_leaves; c->plan_root = tree->root;
+    }
+}
+
+int bvh_intersect(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_ray* d_rays, uint32_t n_rays, bvh_hit* d_hits, int query) {
+    bvh_build_input in;
+    int r = query_check(c, tree, tris, query, d_rays, (uint64_t)n_rays * sizeof(bvh_ray), d_hits, (uint64_t)n_rays * sizeof(bvh_hit), &in); if (r) return r;
     if (n_rays == 0) return 0;
+    const uint32_t n = tree->n_leaves;
     Bind b(c->device);
     hipStream_t s = c->stream;
     const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
     struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    // the stackless pass's parent plan: bvh_refit's, cached for the ctx's own tree under the same rule
-    const bool own = tree->d_nodes == c->nodes;
-    if (!own || c->plan_serial != c->tree_serial || c->plan_n != n || c->plan_root != tree->root) {
-        launch_refit_plan(s, tree->d_nodes, n, tree->root, c->parent);
-        c->plan_serial = own ? c->tree_serial : 0; c->plan_n = n; c->plan_root = tree->root;
-    }
+    query_plan(c, tree, s);
     u32* overflow = c->small + 58;                            // rays left to the stackless pass
     hipError_t e = hipMemsetAsync(overflow, 0, sizeof(u32), s);
     if (e == hipSuccess) {
         launch_intersect(s, (int)tree->layout, query, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_rays, n_rays, tree->d_nodes, tree->d_leaves, n, tree->root, d_hits, overflow, c->parent);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
+    if (install.on) c->recorder.mark(s, nullptr);
+    return 0;
+}
+
+// ---- point queries (no counterpart in the reference) ----------------------------------------------------------------------------------------------
+// bvh_intersect's checks, plan and launch sequence
+int bvh_closest_point(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_point_query* d_points, uint32_t n_points, bvh_point_hit* d_hits,
+                      int query) {
+    bvh_build_input in;
+    int r = query_check(c, tree, tris, query, d_points, (uint64_t)n_points * sizeof(bvh_point_query), d_hits, (uint64_t)n_points * sizeof(bvh_point_hit), &in);
+    if (r) return r;
+    if (n_points == 0) return 0;
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    query_plan(c, tree, s);
+    u32* overflow = c->small + 58;                            // queries left to the stackless pass (bvh_intersect's word: calls on one stream are ordered)
+    hipError_t e = hipMemsetAsync(overflow, 0, sizeof(u32), s);
+    if (e == hipSuccess) {
+        launch_closest_point(s, (int)tree->layout, query, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_points, n_points,
+                             tree->d_nodes, tree->d_leaves, tree->n_leaves, tree->root, d_hits, overflow, c->parent);
         e = hipGetLastError();
     }
     if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }

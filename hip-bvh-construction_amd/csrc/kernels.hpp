@@ -162,6 +162,12 @@ void launch_intersect(hipStream_t s, int layout, int query, int tri_format, cons
                       const void* d_rays, uint32_t n_rays, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root, void* d_hits,
                       uint32_t* d_overflow, const uint32_t* d_parent);
 
+// ---- point queries (point_query.hip): bvh_closest_point's two kernels, arguments as launch_intersect's (d_points: bvh_point_query[n_points], d_hits:
+// bvh_point_hit[n_points]).  k_closest_point (short stack) and k_closest_point_deep (stackless, returns at once while *d_overflow == 0)
+void launch_closest_point(hipStream_t s, int layout, int query, int tri_format, const void* d_tris, const void* d_vertices, const void* d_indices,
+                          uint32_t n_vertices, const void* d_points, uint32_t n_points, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root,
+                          void* d_hits, uint32_t* d_overflow, const uint32_t* d_parent);
+
 // ---- instanced scenes (scene.hip): bvh_scene's kernels.  SceneBlas: the device copy of one validated bvh_blas (64 bytes, read whole when a ray enters an
 // instance); tris = Triangle[n] / float[9n] / the vertices of INDEXED input, idx = INDEXED indices, parent = the BLAS's k_refit_plan plan (u32[2n-1]).
 struct SceneBlas { const void* nodes; const void* leaves; const void* tris; const void* idx; const uint32_t* parent; uint32_t n, root, layout, fmt, nv, pad; };
@@ -208,6 +214,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query(); void warm_optimize(); void warm_scene();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query();
 
 } // namespace bvh

@@ -1,5 +1,5 @@
-// query.hpp — device helpers shared by the ray-query kernels (query.hip: bvh_intersect; scene.hip: bvh_scene_intersect): the hit test, the conservative
-// box test, record / triangle / ray loads.  Compiled with -ffp-contract=off (Makefile): tri_hit is the reference's intersectTriangle operation for operation.
+// query.hpp — device helpers shared by the query kernels (query.hip: bvh_intersect; scene.hip: bvh_scene_intersect; point_query.hip: bvh_closest_point): the
+// hit test, the closest-point formula, the conservative box tests, record / triangle / ray / point loads.  Compiled with -ffp-contract=off (Makefile): tri_hit is the reference's intersectTriangle operation for operation.
 #pragma once
 #include "bvh_mi355x.h"
 #include "common.hpp"
@@ -82,6 +82,66 @@ __device__ __forceinline__ void rec_fetch(const bvh2_node* __restrict__ nodes, c
         w0 = p->prim_idx; w1 = INV;
         b = box_load_u(&p->aabb);
     }
+}
+
+// ---- point queries (point_query.hip: bvh_closest_point) ----------------------------------------------------------------------------------------------------
+constexpr float PQUERY_REL = 0x1p-20f;        // relative slack of the box lower bound (the f32 squared distance errs by < 6 ulp, 2^-20 is 16)
+
+// Ericson's ClosestPtPointTriangle (Real-Time Collision Detection, 5.1.5) with a = v1, b = v2, c = v3, operation for operation (file built with -ffp-contract=off),
+// regions in Ericson's order A, B, AB, C, AC, BC, interior.  Writes the closest point q and the weights (u, v) of b and c; returns dist2 = |p - q|^2.
+__device__ __forceinline__ float tri_closest(QF3 a, QF3 b, QF3 c, QF3 p, QF3& q, float& u, float& v) {
+    const QF3 ab = qsub(b, a), ac = qsub(c, a), ap = qsub(p, a);
+    const float d1 = qdot(ab, ap), d2 = qdot(ac, ap);
+    if (d1 <= 0.0f && d2 <= 0.0f) { q = a; u = 0.0f; v = 0.0f; }
+    else {
+        const QF3 bp = qsub(p, b);
+        const float d3 = qdot(ab, bp), d4 = qdot(ac, bp);
+        const float vc = d1 * d4 - d3 * d2;
+        if (d3 >= 0.0f && d4 <= d3) { q = b; u = 1.0f; v = 0.0f; }
+        else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
+            const float t = d1 / (d1 - d3);
+            q = { a.x + t * ab.x, a.y + t * ab.y, a.z + t * ab.z }; u = t; v = 0.0f;
+        } else {
+            const QF3 cp = qsub(p, c);
+            const float d5 = qdot(ab, cp), d6 = qdot(ac, cp);
+            const float vb = d5 * d2 - d1 * d6;
+            if (d6 >= 0.0f && d5 <= d6) { q = c; u = 0.0f; v = 1.0f; }
+            else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
+                const float w = d2 / (d2 - d6);
+                q = { a.x + w * ac.x, a.y + w * ac.y, a.z + w * ac.z }; u = 0.0f; v = w;
+            } else {
+                const float va = d3 * d6 - d5 * d4, e43 = d4 - d3, e56 = d5 - d6;
+                if (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f) {
+                    const float w = e43 / (e43 + e56);
+                    q = { b.x + w * (c.x - b.x), b.y + w * (c.y - b.y), b.z + w * (c.z - b.z) }; u = 1.0f - w; v = w;
+                } else {
+                    const float denom = 1.0f / ((va + vb) + vc), tv = vb * denom, tw = vc * denom;
+                    q = { (a.x + ab.x * tv) + ac.x * tw, (a.y + ab.y * tv) + ac.y * tw, (a.z + ab.z * tv) + ac.z * tw }; u = tv; v = tw;
+                }
+            }
+        }
+    }
+    const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// conservative distance test of box b against best (a squared distance): true iff the box may hold an accepted candidate; lb_out = the
+// grown box's f32 squared distance, for ordering.  The box grows as in box_pass; fmaxf drops the NaN of a NaN or infinite plane (the axis then costs 0).
+__device__ __forceinline__ bool box_dist_pass(const Box& b, QF3 p, float best, float& lb_out) {
+    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz)));
+    const float dx = fmaxf(fmaxf((b.lx - g) - p.x, p.x - (b.hx + g)), 0.0f);
+    const float dy = fmaxf(fmaxf((b.ly - g) - p.y, p.y - (b.hy + g)), 0.0f);
+    const float dz = fmaxf(fmaxf((b.lz - g) - p.z, p.z - (b.hz + g)), 0.0f);
+    const float lb = (dx * dx + dy * dy) + dz * dz;
+    lb_out = lb;
+    return lb * (1.0f - PQUERY_REL) <= best;
+}
+
+// one bvh_point_query: true iff it is live (no NaN coordinate, radius >= 0); r2 = radius * radius either way (the miss record's dist2)
+__device__ __forceinline__ bool point_load(const bvh_point_query* pts, u32 i, QF3& p, float& r2) {
+    const float4 a = reinterpret_cast<const float4*>(pts)[i];
+    p = { a.x, a.y, a.z }; r2 = a.w * a.w;
+    return !(isnan(a.x) || isnan(a.y) || isnan(a.z)) && a.w >= 0.0f;   // (a NaN radius fails the comparison)
 }
 
 __device__ __forceinline__ bool ray_load(const bvh_ray* rays, u32 i, QRay& r) {

@@ -189,6 +189,12 @@ public:
         check(bvh_intersect(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, d_rays, n, d_hits, static_cast<int>(kind)), "intersect");
     }
 
+    // beyond the reference (bvh_closest_point): closest point / any triangle within each query's radius, against the same tree and triangles as intersect
+    void closestPoint(Context& context, const bvh_point_query* d_points, u32 n, bvh_point_hit* d_hits, bvh_query_kind kind) {
+        check(bvh_closest_point(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, d_points, n, d_hits, static_cast<int>(kind)),
+              "closestPoint");
+    }
+
     // X::traverseBvh(Context&): GenerateRays -> the traversal kernel this builder's reference source selects -> RGBA read-back -> perf block.
     void traverseBvh(Context& context) {
         constexpr TraverseFlavour f = flavour<ALGO>();

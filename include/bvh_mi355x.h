@@ -211,6 +211,36 @@ typedef enum { BVH_QUERY_CLOSEST = 0, BVH_QUERY_ANY = 1 } bvh_query_kind;
 int  bvh_intersect(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
                    const bvh_ray* d_rays, uint32_t n_rays, bvh_hit* d_hits, int query /* bvh_query_kind */);
 
+/* ---- point queries (no counterpart in the reference) -----------------------------------------------------------------------------------
+ * Which point of the mesh is nearest to each query point within its radius (BVH_QUERY_CLOSEST), or is any triangle within the radius (BVH_QUERY_ANY)?  One
+ * bvh_point_hit per query: d_hits[i] answers d_points[i].  Unsigned distance fields, proximity tests, projection onto a surface, ICP correspondences.
+ * tree / tris: exactly as bvh_intersect — any bvh_result in either layout (a build's, a refit's, an optimised or a caller-filled one on the ctx's device),
+ * triangles in any bvh_tri_format (NULL: tree->d_tris is read as Triangle[n_leaves]); the same validation; arrays that are not a tree end in finite time.
+ * Candidate: Ericson's ClosestPtPointTriangle (Real-Time Collision Detection, 5.1.5) in f32, operation for operation, no contraction, a = v1, b = v2, c = v3;
+ * every dot product is (x*x' + y*y') + z*z'; regions tested in Ericson's order: A, B, edge AB, C, edge AC, edge BC, interior; denom = 1.0f / ((va + vb) + vc)
+ * (correctly rounded division).  Point: a, b or c at a vertex; a_k + v*ab_k on AB; a_k + w*ac_k on AC; b_k + w*(c_k - b_k) on BC; (a_k + ab_k*v) + ac_k*w
+ * inside.  (u, v) = the weights of v2 and v3: (0,0) at A, (1,0) at B, (0,1) at C, (v,0) on AB, (0,w) on AC, (1.0f - w, w) on BC, (v, w) inside.
+ * dist2 = (dx*dx + dy*dy) + dz*dz with d = point - p.  (The formula is the contract even where it is inexact: on a collinear triangle, rounding noise in
+ * va, vb, vc can select the interior branch, whose point then lies on the triangle's line but not necessarily on the triangle.)
+ * Acceptance: a candidate is accepted iff dist2 <= r2, r2 = radius*radius in f32 (NaN is never accepted; an infinite radius is no bound).  Queries with a NaN
+ * coordinate, a NaN radius or radius < 0 miss.
+ * BVH_QUERY_CLOSEST: the accepted candidate with the smallest (dist2, prim_idx), compared lexicographically — the answer does not depend on the builder, the
+ * layout, the traversal order or the input format.  BVH_QUERY_ANY: some accepted candidate (traversal stops at the first): "is anything within r".
+ * A hit is written as {point, dist2, u, v, prim_idx, 0}; a miss as {0, 0, 0, r2, 0, 0, BVH_INVALID, 0}.
+ * Box tests are conservative: every box grows on every axis by 2^-16 times its largest |coordinate|, its f32 squared distance to the point is
+ * lb, and the subtree is kept iff lb * (1 - 2^-20) <= the best dist2 so far (r2 at the start).  Answers are exact on well-conditioned queries: the f64
+ * squared distance from the point to the closest answer's triangle box grown by 2^-17 times its largest |coordinate| is <= that answer's dist2.  On every
+ * query a reported hit is an accepted candidate, and a closest answer is never below the true best.
+ * Errors (nothing is written): NULL ctx / tree / d_points / d_hits, n_leaves < 2, layout not 0 or 1, NULL d_nodes, layout 1 with NULL d_leaves, root not an
+ * internal node, no triangles (tris NULL and tree->d_tris NULL) or a tris format error, query not 0 or 1, overlapping d_points / d_hits ranges:
+ * BVH_E_INVALID_ARG.  n_leaves larger than the ctx's capacity: BVH_E_INVALID_ARG (the parent plan lives in the arena; call bvh_ctx_reserve first).
+ * n_points == 0: 0, nothing is touched.
+ * Asynchronous on the ctx's stream, no read-back.  There is no depth limit: queries whose short stack would overflow are finished by a stackless pass through
+ * bvh_refit's parent plan, cached for the ctx's own tree as for bvh_intersect.  bvh_ctx_kernel_times reports k_closest_point, k_closest_point_deep and, when
+ * the plan is made, k_refit_plan. */
+int  bvh_closest_point(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
+                       const bvh_point_query* d_points, uint32_t n_points, bvh_point_hit* d_hits, int query /* bvh_query_kind */);
+
 /* ---- tree optimisation (no counterpart in the reference) ---------------------------------------------------------------------------------
  * Lower a built tree's SAH by treelet restructuring (Karras & Aila, HPG 2013): bottom-up, every treelet of 7 entries whose root holds enough leaves is replaced
  * by its SAH-optimal topology over the same entries.  The fast LBVH builds come out close to HPLOC quality; PLOC++ / HPLOC trees gain a few percent.
