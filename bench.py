@@ -7,17 +7,20 @@ N > 1: one process per GPU (launched by torch.distributed.run), every rank build
 seed) — the path shards at scene granularity, no data-path collective; the only exchange is an all-gather of the 24-byte
 root AABBs (RCCL) per step.  scaling = weak.  value = triangles built by all ranks / time of K steps (max over ranks).
 
-Also reported on the same JSON line:
+A plain run does what that value needs and no more: set up, warm up, time the K steps, write --dump-outputs, print the line.  Its line carries what the timed
+steps themselves yield: the value, ms_per_step, and from the HIP events recorded inside the timed region kernel_ms_per_step and
   roofline     — dominant kernel's algorithmic bytes / its HIP-event time (events recorded on the launch stream inside the
                  timed region) against the 8 TB/s HBM peak; roofline.issue = how busy the VALUs and the LDS pipe are in that kernel
-                 (from the committed counter file profiles/issue_counters.json: the second bound of a kernel that is not HBM-bound);
+                 (from the committed counter file profiles/issue_counters.json: the second bound of a kernel that is not HBM-bound).
+--full adds every measurement that takes a run of its own (null on the line of a plain run):
+  stage_ms, sah_bvh2 — one extra build of the benchmark mesh with stage events (reference Timer tokens), and the SAH cost of its tree;
   cpu_baseline — the reference's CPU binned-SAH builder (oracle port, 1 thread) timed on a bounded sample of the same mesh;
   secondary    — (N = 1) the other BASELINE.json configs at their own sizes, 50-build loops after the timed region: Sponza-class 262 144 single-pass LBVH (config 2),
                  Sponza-class 262 144 PLOC++ + the BVH4 collapse (config 4), uniform 2 M HPLOC (config 5's per-GPU mesh), each with the FIRST build of that size on a
                  fresh context beside the warm loop (the library sizes some launch batches from the previous same-size build);
   config5      — (N > 1) the same exchange with config 5's own shape: 2 M triangles per GPU, seed 100 + rank, offset (rank, 0, 0).
 --dump-outputs DIR writes rank 0's last timed build (sort, leaves, numbering-independent node rows; a fixed sample at large sizes) as .npy files:
-the meshes are seeded, so two builds of the project run with the same arguments can be compared output for output (dump_outputs).
+the meshes are seeded, so two builds of the project run with the same arguments can be compared output for output (dump_outputs); the same files with and without --full.
 Algorithmic bytes of the PLOC-family emit stages are exact per mesh: profiles/algorithmic_bytes.json, written by
 tools/algorithmic_bytes.py from the pinned oracle's cluster-load / store counts; the split of the HPLOC emit between its two kernels is the
 measured task share of profiles/hploc_task_share.json (tools/measure_task_share.py).  Both are data files: nothing here calls the oracle outside
@@ -238,7 +241,7 @@ def dump_outputs(res: dict, out_dir: str) -> dict:
     return out
 
 
-def main() -> None:
+def parse_args(argv=None) -> argparse.Namespace:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="timed builds (200 x ~1.5 ms: a 0.3 s timed region, so that one slow launch does not move the number)")
@@ -246,13 +249,20 @@ def main() -> None:
     ap.add_argument("--tris", type=int, default=10_000_000)
     ap.add_argument("--algo", default="hploc", choices=["hploc", "ploc", "lbvh_single", "lbvh_two"])
     ap.add_argument("--mesh", default="uniform", choices=["uniform", "bunny", "sponza"])
-    ap.add_argument("--cpu-sample", type=int, default=10_000_000, help="triangles of the mesh the CPU baseline is timed on (0 = skip); the whole 10 M mesh is ~25 s of single-thread work")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run what the headline value does not need: the stage-timed build and its SAH cost, the other configs' loops (N = 1) / "
+                                                        "the config-5-shaped exchange (N > 1), the CPU baseline")
+    ap.add_argument("--cpu-sample", type=int, default=10_000_000, help="--full: triangles of the mesh the CPU baseline is timed on (0 = skip); the whole 10 M mesh is ~25 s of single-thread work")
     ap.add_argument("--no-kernel-events", action="store_true", help="do not bracket kernels with HIP events in the timed region")
-    ap.add_argument("--no-secondary", dest="secondary", action="store_false", help="skip the other configs' loops (N = 1) / the config-5-shaped exchange (N > 1)")
+    ap.add_argument("--no-secondary", dest="secondary", action="store_false", help="--full: skip the other configs' loops (N = 1) / the config-5-shaped exchange (N > 1)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the result of the last timed build as .npy files to DIR (see dump_outputs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def main() -> None:
+    args = parse_args()
 
     import torch
     import bvh_pkg
@@ -362,14 +372,16 @@ def main() -> None:
         assert torch.equal(gathered[6 * rank: 6 * rank + 6], root_box), "all-gather of root AABBs is inconsistent"
     if args.dump_outputs and rank == 0:                      # the last timed build's result, before the extra build below replaces it
         dump_outputs(builder.download(), args.dump_outputs)
-    ctx.set_kernel_sampling(1); ctx.set_profiling(1)
-    builder.build(ctx, d_tris, on_device=True, n=n)          # one extra build with stage events (reference Timer tokens)
-    stage = dict(builder.m_timer)
-    sah = builder.sah_cost()
+    stage = sah = None
+    if args.full:
+        ctx.set_kernel_sampling(1); ctx.set_profiling(1)
+        builder.build(ctx, d_tris, on_device=True, n=n)      # one extra build with stage events (reference Timer tokens)
+        stage = dict(builder.m_timer)
+        sah = builder.sah_cost()
 
     # ---- BASELINE.json config 5 at its own shape (N > 1 lines carry it next to the 10 M weak-scaling value): 2 M triangles per GPU, seed 100 + rank, offset (rank, 0, 0)
     config5 = None
-    if gather and args.secondary:
+    if args.full and gather and args.secondary:
         n5 = 2_000_000
         tris5 = pkg.meshgen.uniform(n5, 100 + rank, offset=(float(rank), 0.0, 0.0))
         d5 = torch.from_numpy(tris5.view(np.uint8).reshape(-1)).cuda()
@@ -449,12 +461,12 @@ def main() -> None:
             roof["own_bytes_per_launch"] = own; roof["own_frac"] = round(own / (per_build_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
     # ---- the other configs on the record (N = 1): after the timed region, before the CPU baseline
     secondary = None
-    if world == 1 and args.secondary:
+    if args.full and world == 1 and args.secondary:
         del d_tris; torch.cuda.empty_cache()
         secondary = run_secondary(pkg, torch, local)
     # ---- CPU baseline: reference's binned-SAH builder (oracle port), single thread, bounded sample of the same mesh
     cpu = None
-    if args.cpu_sample > 0 and world == 1:                 # (rank 0 at N = 1 only: an N-GPU run does not hold its ranks for 23 s of CPU work)
+    if args.full and args.cpu_sample > 0 and world == 1:                 # (rank 0 at N = 1 only: an N-GPU run does not hold its ranks for 23 s of CPU work)
         import oracle as orc
         m = min(args.cpu_sample, n)
         sample = np.ascontiguousarray(tris[:m])
@@ -465,16 +477,16 @@ def main() -> None:
                "sample": (f"the whole {m}-triangle benchmark mesh" if m == n else f"first {m} triangles of the benchmark mesh") + f", oracle port of SahBvh::build (src/BinnedSahBvh.cpp:13-203), {dt:.1f} s",
                "sah": round(orc.sah_binned(nodes, total, m)[0], 4)}
     out = {
-        "metric": "bvh_build_throughput", "value": round(value, 2), "unit": "Mtris/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "metric": "bvh_build_throughput", "value": round(value, 2), "unit": "Mtris/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32+u32",
         "data": "synthetic",
         "config": {"workload": workload, "builder": pkg.ALGO_NAMES[algo], "tris_per_gpu": n, "mesh": args.mesh,
                    "seed": "1+rank", "parallelism": f"scene-shard x{world}" + (" + allgather(root aabb)" if world > 1 else "")},
-        "stage_ms": {k: round(v, 4) for k, v in stage.items()},
+        "stage_ms": {k: round(v, 4) for k, v in stage.items()} if stage is not None else None,
         "kernel_ms_per_step": {k: round(v[0] / n_sampled, 4) for k, v in ktimes.items()},     # from the sampled builds of the timed region
         "kernel_event_sampling": f"every {sample_every}th of the {args.steps} timed builds, the first timed build included" + (f" ({n_sampled} builds)" if sample_every > 1 else "")
                                  + "; a sampled build carries one event per launch and is stretched by them: the sum of kernel_ms_per_step exceeds ms_per_step",
-        "sah_bvh2": round(sah, 4),
+        "sah_bvh2": round(sah, 4) if sah is not None else None,
         "pipeline_roofline": {"algorithmic_bytes": pipeline_bytes, "source": ("exact: " + ex[3]) if ex else "SURVEY.md 8(d) constants (bvh_timings.bytes_algorithmic)",
                               "achieved_GBs": round(pipeline_bytes / (ms_per_step * 1e-3) / 1e9, 1),
                               "frac": round(pipeline_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},

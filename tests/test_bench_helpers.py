@@ -43,6 +43,14 @@ def test_bench_helpers_read_the_data_files():
     assert b.kernel_bytes_per_prim("k_hploc_block", "hploc", "no_such_workload")[0] == 177.9   # falls back to the survey constants
 
 
+def test_bench_full_is_an_option_and_off_by_default():
+    b = _bench()
+    plain = b.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False and (plain.gpus, plain.steps, plain.warmup, plain.dump_outputs) == (1, 20, 5, None)
+    full = b.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full is True and {k: v for k, v in vars(full).items() if k != "full"} == {k: v for k, v in vars(plain).items() if k != "full"}
+
+
 def test_issue_counter_file_is_recomputable():
     ic = json.load(open(os.path.join(ROOT, "profiles", "issue_counters.json")))
     e = ic["k_hploc_block@10000000"]

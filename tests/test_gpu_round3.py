@@ -56,7 +56,7 @@ def test_bench_nccl_two_ranks_sharing_one_device_attempt():
         pytest.skip("two devices are visible: test_bench_nccl_two_ranks_when_two_devices covers the real thing")
     env = dict(os.environ); env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0"); env["NCCL_DEBUG"] = "WARN"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--tris", "200000", "--steps", "3", "--warmup", "1", "--cpu-sample", "0"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--tris", "200000", "--steps", "3", "--warmup", "1", "--full", "--cpu-sample", "0"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
     except subprocess.TimeoutExpired:
@@ -99,6 +99,49 @@ def test_bench_dump_outputs(pkg, orc, ctx, tmp_path):
         assert got.dtype in (np.float32, np.float64) and got.dtype == a.dtype and np.array_equal(got, a), name
     fe = orc.front_end(tris, 30)
     assert np.array_equal(here["sorted_keys"], fe["skeys"].astype(np.float64)) and np.array_equal(here["sorted_vals"], fe["svals"].astype(np.float64))
+
+
+FULL_ONLY = ("stage_ms", "sah_bvh2", "cpu_baseline", "secondary", "config5")          # what a line carries only when the run was asked for it with --full
+
+
+def _run_plain_bench(*args):
+    """bench.py in a new process, the benchmark's own command line: (its one JSON line, seconds from start to exit)"""
+    import time
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0]), wall
+
+
+def test_bench_plain_run_is_lean():
+    """`bench.py --gpus 1 --steps N --warmup W` at the benchmark's own size: the headline fields, what the timed region's events give, and none of the legs that
+    take runs of their own; the whole process, start to exit, spends at most 30 s outside its N + W steps"""
+    steps, warmup = 20, 5
+    out, wall = _run_plain_bench("--gpus", "1", "--steps", str(steps), "--warmup", str(warmup))
+    assert out["metric"] == "bvh_build_throughput" and out["unit"] == "Mtris/s" and out["higher_is_better"] is True and out["dtype"] == "f32+u32"
+    assert out["steps"] == steps and out["warmup"] == warmup and out["full"] is False and out["config"]["workload"] == "uniform_10000000_tris_hploc"
+    assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(10_000_000 / out["ms_per_step"] / 1e3, rel=1e-3)
+    assert out["roofline"]["kernel"].startswith("k_") and out["kernel_ms_per_step"]
+    assert all(out[k] is None for k in FULL_ONLY), {k: out[k] for k in FULL_ONLY}
+    outside = wall - (steps + warmup) * out["ms_per_step"] * 1e-3
+    print(f"plain run: {wall:.2f} s from start to exit, {outside:.2f} s outside its steps (mesh generation {out['mesh_gen_s']} s)")
+    assert outside <= 30.0
+
+
+def test_bench_full_runs_every_leg():
+    """--full: the same line with the stage-timed build, the SAH cost, the other configs' loops and the CPU baseline (a small mesh and sample keep the test short)"""
+    out, _ = _run_plain_bench("--gpus", "1", "--tris", "200000", "--steps", "3", "--warmup", "1", "--full", "--cpu-sample", "20000")
+    assert out["full"] is True and out["steps"] == 3 and out["ms_per_step"] > 0 and out["roofline"]["kernel"].startswith("k_")
+    assert out["stage_ms"]["TotalTime"] > 0 and out["sah_bvh2"] > 0
+    assert out["cpu_baseline"]["value"] > 0 and out["cpu_baseline"]["sample"].startswith("first 20000 triangles")
+    assert [e["workload"] for e in out["secondary"]] == ["sponza_262144_tris_lbvh_single", "sponza_262144_tris_ploc", "uniform_2000000_tris_hploc"]
+    assert all(e["ms_per_step"] > 0 and e["cold_first_build_ms"] > 0 for e in out["secondary"]) and out["config5"] is None      # (config5 belongs to N > 1)
+    # the options that shape those legs still switch them off one by one
+    out, _ = _run_plain_bench("--gpus", "1", "--tris", "200000", "--steps", "3", "--warmup", "1", "--full", "--cpu-sample", "0", "--no-secondary")
+    assert out["full"] is True and out["stage_ms"]["TotalTime"] > 0 and out["sah_bvh2"] > 0 and out["cpu_baseline"] is None and out["secondary"] is None
 
 
 def test_ctx_options_replace_env_knobs(pkg, orc, ctx):

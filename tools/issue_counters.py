@@ -23,7 +23,7 @@ def main():
         if k not in CONST or counter not in WANT:
             continue
         e = out.setdefault(f"{k}@{n}", {"shader_engines": 32, "simds": 1024, "cus": 256, "cycles_per_valu_inst": CONST[k][0], "cycles_per_lds_inst": CONST[k][1],
-                                          "launches_averaged": cnt, "source": "rocprofv3 --pmc " + " ".join(WANT) + " -- python bench.py --steps 3 --warmup 1 --cpu-sample 0 --no-kernel-events"})
+                                          "launches_averaged": cnt, "source": "rocprofv3 --pmc " + " ".join(WANT) + " -- python bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --no-kernel-events"})
         e[counter] = avg
     for k, e in out.items():
         if k.startswith("_"):
