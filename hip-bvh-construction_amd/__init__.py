@@ -74,7 +74,7 @@ EXPORTS = [
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas",
-    "bvh_closest_point",
+    "bvh_closest_point", "bvh_overlap",
 ]
 
 
@@ -111,6 +111,7 @@ class BatchReport(C.Structure):
 TRI_PADDED64, TRI_PACKED36, TRI_INDEXED = 0, 1, 2
 QUERY_CLOSEST, QUERY_ANY = 0, 1      # bvh_query_kind
 _QUERY_IDS = {"closest": QUERY_CLOSEST, "any": QUERY_ANY}
+OVERLAP_BOXES, OVERLAP_SELF = 0, 1   # bvh_overlap_mode
 ABI_VERSION = 4                      # BVH_ABI_VERSION of include/bvh_mi355x.h this binding was written against
 # bvh_option (bvh_ctx_set_option) and the names this harness accepts for the values
 OPT_HPLOC_SCHEDULER, OPT_LBVH_SCHEDULER, OPT_SORT_TEST_KNOBS, OPT_PLOC_SCHEDULER = 0, 1, 2, 3
@@ -203,6 +204,7 @@ def lib() -> C.CDLL:
         "bvh_scene_intersect": ([vp, vp, u32, vp, i32], i32),
         "bvh_scene_tlas": ([vp, C.POINTER(Result)], i32),
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
+        "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -524,6 +526,56 @@ class _Builder:
             return hits.download(POINT_HIT, n_points)
         finally:
             hits.free()
+            if own is not None:
+                own.free()
+
+    def overlap(self, boxes=None, self_pairs: bool = False, capacity: int | None = None, n: int | None = None):
+        """bvh_overlap on this builder's tree: which primitives' boxes each query box touches.  ``boxes`` a host AABB array, a host (m, 6) float array
+        (min xyz, max xyz), or a device buffer of bvh_aabb records (DeviceBuffer / int address, with ``n``).  ``self_pairs=True`` is BVH_OVERLAP_SELF: ``boxes``
+        defaults to the result's own d_prim_aabbs and only primitives above the query's index are reported.  Returns host arrays (offsets u32[m + 1], prims
+        u32[total]): query i's primitives are prims[offsets[i]:offsets[i + 1]], in no particular order.  ``capacity`` is the first guess of the total (default
+        8 per query); when it is too small the call is repeated with the total it reported."""
+        if self._ctx is None:
+            raise BvhError("overlap needs a built tree")
+        ctx = self._ctx
+        own = None
+        if boxes is None:
+            if not self_pairs or not self.result.d_prim_aabbs:
+                raise BvhError("boxes are required (only self_pairs=True defaults them to the tree's own primitive boxes)")
+            boxes, n = self.result.d_prim_aabbs, self.result.n_leaves
+        elif isinstance(boxes, np.ndarray):
+            if boxes.dtype != AABB:
+                f = np.asarray(boxes, dtype=np.float32)
+                if f.ndim != 2 or f.shape[1] != 6:
+                    raise BvhError("boxes must have dtype AABB or shape (m, 6)")
+                boxes = np.ascontiguousarray(f).view(AABB).reshape(-1)
+            n = boxes.shape[0]
+            own = boxes = ctx.upload(np.ascontiguousarray(boxes)) if n else None
+        elif n is None:
+            n = boxes.nbytes // AABB.itemsize if isinstance(boxes, DeviceBuffer) else None
+            if n is None:
+                raise BvhError("n is required for device boxes")
+        mode = OVERLAP_SELF if self_pairs else OVERLAP_BOXES
+        what = f"{ALGO_NAMES[self.ALGO]}::overlap"
+        if n == 0 and not self_pairs:                     # no queries: the empty answer, without a call
+            return np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=np.uint32)
+        offsets = ctx.alloc((n + 1) * 4)
+        prims = None
+        try:
+            cap = max(int(capacity) if capacity is not None else 8 * n, 1)
+            total = C.c_uint64()
+            for _ in range(2):
+                prims = ctx.alloc(cap * 4)
+                _check(lib().bvh_overlap(ctx.handle, C.byref(self.result), _ptr(boxes), n, mode, offsets.ptr, prims.ptr, cap, C.byref(total)), what)
+                if total.value <= cap:
+                    break
+                prims.free(); prims = None
+                cap = total.value
+            return offsets.download(np.uint32, n + 1), prims.download(np.uint32, total.value)
+        finally:
+            offsets.free()
+            if prims is not None:
+                prims.free()
             if own is not None:
                 own.free()
 

@@ -63,6 +63,7 @@ struct bvh_ctx {
     HplocScratch hploc{};             //               (hploc.dep is zeroed when the arena is allocated and stays clean)
     PlocScratch ploc{};
     u32* small = nullptr;             // 64 words: [0] root, [1] hploc node counter, [8..9] f64 SAH
+    u64* overlap_sums = nullptr;      // OVERLAP_SCAN_BLOCKS  (bvh_overlap's scan: chunk sums)
     size_t lbvh_queue_capacity = 0;   // uint4 entries of ploc.list0 (>= kernels.hpp lbvh_queue_capacity(cap))
     // The emitters' self-cleaning scratch (hploc.dep / LBVH slots all-zero, two-pass flags all-ones) is only clean after a build that ran to
     // completion.  Set while an emit is being enqueued, cleared when every launch of it was accepted: a build that failed in between
@@ -193,8 +194,9 @@ void carve(bvh_ctx* c, char* base, uint32_t cap, size_t* total) {
     c->ploc.ids1 = k.take<u32>(n);
     c->ploc.status = k.take<u64>((size_t)PLOC_MAX_ITERS * ploc_chunks(cap));
     c->ploc.state = k.take<u32>(PLOC_STATE_WORDS);
-    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's / bvh_closest_point's overflow count
+    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's / bvh_closest_point's overflow count (bvh_overlap: [58] count pass, [59] fill pass, [60..61] u64 total)
     c->hploc.zero_parent = c->small + 1;
+    c->overlap_sums = k.take<u64>(OVERLAP_SCAN_BLOCKS);
     *total = k.off;
 }
 
@@ -385,7 +387,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); }); }
     *out = c;
     return 0;
 }
@@ -824,6 +826,59 @@ int bvh_closest_point(bvh_ctx* c, const bvh_result* tree, const bvh_build_input*
     }
     if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
     if (install.on) c->recorder.mark(s, nullptr);
+    return 0;
+}
+
+// ---- box queries (no counterpart in the reference) ------------------------------------------------------------------------------------------------
+// count -> scan -> fill on one stream; every argument is checked before anything is enqueued, so an error writes nothing.  The arena is never re-allocated (the
+// tree may point into it).  Whether the fill runs is decided on the device (overlap.hip); the host only waits when the caller asks for the total.
+int bvh_overlap(bvh_ctx* c, const bvh_result* tree, const bvh_aabb* d_boxes, uint32_t n_boxes, int mode, uint32_t* d_offsets, uint32_t* d_prims,
+                uint64_t capacity, uint64_t* total_out) {
+    if (!c || !tree || !d_boxes || !d_offsets) return BVH_E_INVALID_ARG;
+    const uint32_t n = tree->n_leaves;
+    if (n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1) return BVH_E_INVALID_ARG;
+    if (mode != BVH_OVERLAP_BOXES && mode != BVH_OVERLAP_SELF) return BVH_E_INVALID_ARG;
+    if (mode == BVH_OVERLAP_SELF && n_boxes != n) return BVH_E_INVALID_ARG;
+    if (n_boxes >= (1u << 30)) return BVH_E_INVALID_ARG;
+    if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
+    {   // the three caller arrays must not overlap (d_prims is never written past 2^32 - 1 words: a larger total skips the fill)
+        struct Range { uintptr_t lo, hi; };
+        const uint64_t prim_words = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;
+        const Range rb{ (uintptr_t)d_boxes, (uintptr_t)d_boxes + (uint64_t)n_boxes * sizeof(bvh_aabb) };
+        const Range ro{ (uintptr_t)d_offsets, (uintptr_t)d_offsets + ((uint64_t)n_boxes + 1u) * sizeof(u32) };
+        const Range rp{ (uintptr_t)d_prims, (uintptr_t)d_prims + (d_prims ? prim_words * sizeof(u32) : 0u) };
+        auto cross = [](const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; };
+        if (cross(rb, ro) || cross(rb, rp) || cross(ro, rp)) return BVH_E_INVALID_ARG;
+    }
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    if (n_boxes == 0) {                                       // d_offsets[0] = total = 0, nothing else
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
+        if (total_out) *total_out = 0;
+        return 0;
+    }
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    query_plan(c, tree, s);
+    u32* const overflow = c->small + 58;                      // [0] count pass, [1] fill pass: queries left to the stackless pass
+    u64* const total = reinterpret_cast<u64*>(c->small + 60);
+    hipError_t e = hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s);
+    if (e == hipSuccess) {
+        launch_overlap_count(s, (int)tree->layout, mode, d_boxes, n_boxes, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, overflow, c->parent,
+                             c->overlap_sums, total);
+        if (d_prims)
+            launch_overlap_fill(s, (int)tree->layout, mode, d_boxes, n_boxes, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, d_prims, capacity, total,
+                                overflow + 1, c->parent);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
+    if (install.on) c->recorder.mark(s, nullptr);
+    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
+        u32* const rb = c->h_pinned + 8;
+        const int r = read_back(c, c->small + 60, 2, nullptr, 0, rb); if (r) return r;
+        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
+        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
+    }
     return 0;
 }
 

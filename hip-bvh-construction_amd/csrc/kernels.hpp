@@ -168,6 +168,18 @@ void launch_closest_point(hipStream_t s, int layout, int query, int tri_format, 
                           uint32_t n_vertices, const void* d_points, uint32_t n_points, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root,
                           void* d_hits, uint32_t* d_overflow, const uint32_t* d_parent);
 
+// ---- box queries (overlap.hip): bvh_overlap's kernels.  launch_overlap_count: k_overlap_count (short stack; d_offsets[i] = query i's count) + k_overlap_deep
+// (stackless, returns at once while *d_overflow == 0) + k_overlap_scan (two launches: the counts become u32[n_boxes + 1] offsets in place, saturated at
+// 0xFFFFFFFF, and *d_total the 64-bit total; d_sums: u64[OVERLAP_SCAN_BLOCKS] scratch).  launch_overlap_fill: k_overlap_fill + k_overlap_deep, which return at
+// once unless *d_total <= capacity and *d_total < 2^32; query i's primitives go to d_prims[d_offsets[i] ..].  Each pass has an overflow word of its own, zeroed
+// before the launches.  mode: bvh_overlap_mode
+constexpr uint32_t OVERLAP_SCAN_BLOCKS = 1024;
+void launch_overlap_count(hipStream_t s, int layout, int mode, const void* d_boxes, uint32_t n_boxes, const void* d_nodes, const void* d_leaves, uint32_t n,
+                          uint32_t root, uint32_t* d_offsets, uint32_t* d_overflow, const uint32_t* d_parent, uint64_t* d_sums, uint64_t* d_total);
+void launch_overlap_fill(hipStream_t s, int layout, int mode, const void* d_boxes, uint32_t n_boxes, const void* d_nodes, const void* d_leaves, uint32_t n,
+                         uint32_t root, uint32_t* d_offsets, uint32_t* d_prims, uint64_t capacity, const uint64_t* d_total, uint32_t* d_overflow,
+                         const uint32_t* d_parent);
+
 // ---- instanced scenes (scene.hip): bvh_scene's kernels.  SceneBlas: the device copy of one validated bvh_blas (64 bytes, read whole when a ray enters an
 // instance); tris = Triangle[n] / float[9n] / the vertices of INDEXED input, idx = INDEXED indices, parent = the BLAS's k_refit_plan plan (u32[2n-1]).
 struct SceneBlas { const void* nodes; const void* leaves; const void* tris; const void* idx; const uint32_t* parent; uint32_t n, root, layout, fmt, nv, pad; };
@@ -214,6 +226,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap();
 
 } // namespace bvh

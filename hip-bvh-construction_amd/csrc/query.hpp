@@ -137,6 +137,15 @@ __device__ __forceinline__ bool box_dist_pass(const Box& b, QF3 p, float best, f
     return lb * (1.0f - PQUERY_REL) <= best;
 }
 
+// ---- box queries (overlap.hip: bvh_overlap) -----------------------------------------------------------------------------------------------------------------
+// closed, non-empty boxes: comparisons only, no arithmetic, so nothing is conservative here.  Touching boxes overlap, -0 == +0, a NaN anywhere fails, and an
+// inverted box (a min above its max: the empty set, such as the reset box) overlaps nothing.  Monotone under containment: a box that contains a passing box
+// passes, which is all the traversal needs.
+__device__ __forceinline__ bool box_valid(const Box& b) { return b.lx <= b.hx && b.ly <= b.hy && b.lz <= b.hz; }
+__device__ __forceinline__ bool box_overlap(const Box& q, const Box& b) {
+    return q.lx <= b.hx && b.lx <= q.hx && q.ly <= b.hy && b.ly <= q.hy && q.lz <= b.hz && b.lz <= q.hz && box_valid(q) && box_valid(b);
+}
+
 // one bvh_point_query: true iff it is live (no NaN coordinate, radius >= 0); r2 = radius * radius either way (the miss record's dist2)
 __device__ __forceinline__ bool point_load(const bvh_point_query* pts, u32 i, QF3& p, float& r2) {
     const float4 a = reinterpret_cast<const float4*>(pts)[i];

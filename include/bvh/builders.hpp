@@ -195,6 +195,18 @@ public:
               "closestPoint");
     }
 
+    // beyond the reference (bvh_overlap): which primitives' boxes each query box touches, as offsets + primitive indices; BVH_OVERLAP_SELF with the tree's own
+    // primitive boxes gives every overlapping pair once.  d_prims NULL: count only.  Returns the total (the call waits for it)
+    u64 overlap(Context& context, const bvh_aabb* d_boxes, u32 n, bvh_overlap_mode mode, u32* d_offsets, u32* d_prims, u64 capacity) {
+        uint64_t total = 0;
+        check(bvh_overlap(context.handle(), &m_result, d_boxes, n, static_cast<int>(mode), d_offsets, d_prims, capacity, &total), "overlap");
+        return total;
+    }
+    // the asynchronous form: no read-back, the fill decides on the device whether the capacity suffices
+    void overlapAsync(Context& context, const bvh_aabb* d_boxes, u32 n, bvh_overlap_mode mode, u32* d_offsets, u32* d_prims, u64 capacity) {
+        check(bvh_overlap(context.handle(), &m_result, d_boxes, n, static_cast<int>(mode), d_offsets, d_prims, capacity, nullptr), "overlap");
+    }
+
     // X::traverseBvh(Context&): GenerateRays -> the traversal kernel this builder's reference source selects -> RGBA read-back -> perf block.
     void traverseBvh(Context& context) {
         constexpr TraverseFlavour f = flavour<ALGO>();

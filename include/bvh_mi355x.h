@@ -241,6 +241,42 @@ int  bvh_intersect(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* 
 int  bvh_closest_point(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
                        const bvh_point_query* d_points, uint32_t n_points, bvh_point_hit* d_hits, int query /* bvh_query_kind */);
 
+/* ---- box queries (no counterpart in the reference) -------------------------------------------------------------------------------------
+ * Which primitives does each box touch?  The broad phase of collision detection, region selection, culling against an axis-aligned volume, neighbour gathering
+ * on a bvh_build_boxes tree, "which instances does this volume touch" on a scene's top-level tree.
+ * tree: any bvh_result bvh_intersect accepts, in either layout, read as it is — a build's, a refit's, an optimised one, a bvh_build_boxes tree, a
+ * bvh_scene_tlas result, or caller-filled device arrays.  Only root, n_leaves, layout, d_nodes and d_leaves are read; no triangles are needed; nothing in the
+ * tree is written.  A primitive's box is its leaf record's box (layout 0: node n-1+j; layout 1: d_leaves[j].aabb).
+ * Overlap test: closed, non-empty boxes, IEEE f32 comparisons only, no arithmetic.  q overlaps b iff, for k = x, y, z,
+ *   q.min.k <= b.max.k && b.min.k <= q.max.k && q.min.k <= q.max.k && b.min.k <= b.max.k.
+ * Touching boxes (a shared face, edge or corner) overlap.  A NaN anywhere makes the test false.  An inverted box (a min above its max: the empty set, such as
+ * the reset box) overlaps nothing — for boxes that are not inverted the last two comparisons hold and the test is the usual six.  -0 equals +0.
+ * Answer: query i's set is every primitive whose leaf box overlaps d_boxes[i], in compressed-row form: d_prims[d_offsets[i] .. d_offsets[i+1]) is query i's
+ * slice, d_offsets[0] = 0, d_offsets[n_boxes] = the total.  The set is exact for EVERY query and does not depend on the builder, the layout or the scheduler.
+ * The order inside a slice is unspecified, but the same call on the same arrays gives the same bytes.  Each primitive appears at most once per slice.
+ * Exactness condition: every internal box contains its children's boxes (then a box that a leaf's box passes is passed by every box above it).  All trees this
+ * library produces satisfy it bitwise: an internal box is the fminf / fmaxf union of its children's.  On caller-filled trees that violate it every reported
+ * primitive still overlaps its query, but some may be left out.  Arrays that are not a tree end in finite time with unspecified answers (d_prims is never
+ * written outside query i's slice).  A child or primitive index out of range is never followed or reported.
+ * BVH_OVERLAP_SELF: n_boxes must equal n_leaves; d_boxes[i] is taken as primitive i's box (typically tree->d_prim_aabbs) and only primitives j > i are
+ * reported, so every unordered overlapping pair {i, j} appears exactly once, as j in i's slice, and no primitive pairs with itself.
+ * Passes: the call always counts, then scans the counts into d_offsets, and keeps the 64-bit total in a device word.  It fills d_prims iff d_prims != NULL,
+ * total <= capacity and total < 2^32; that decision is made ON THE DEVICE (the fill launch reads the total word and returns at once), so the call stays
+ * asynchronous on the ctx's stream.  If the fill is skipped d_prims is not touched and d_offsets is still complete.  With total_out != NULL the call blocks on
+ * an 8-byte read-back into pinned words and stores the total; a host that guessed too small a capacity re-allocates and calls again.  A total of 2^32 or more
+ * saturates d_offsets at 0xFFFFFFFF; if total_out was given the call then returns BVH_E_TOO_LARGE (with *total_out set).
+ * There is no depth limit: a query whose short stack would overflow is finished by a stackless pass through bvh_refit's parent plan, cached for the ctx's own
+ * tree as for bvh_intersect and made per call for caller-owned arrays.  Count and fill agree on every query's set whichever pass served it.
+ * Errors (nothing is written or enqueued, BVH_E_INVALID_ARG): NULL ctx / tree / d_boxes / d_offsets, n_leaves < 2, layout not 0 or 1, NULL d_nodes, layout 1
+ * with NULL d_leaves, root not an internal node, mode not 0 or 1, BVH_OVERLAP_SELF with n_boxes != n_leaves, n_boxes >= 2^30, n_leaves larger than the ctx's
+ * capacity (the parent plan lives in the arena; call bvh_ctx_reserve first), d_offsets or d_prims (capacity words) overlapping d_boxes or each other.
+ * n_boxes == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.
+ * bvh_ctx_kernel_times reports k_overlap_count, k_overlap_deep (after each pass), k_overlap_scan, k_overlap_fill and, when the plan is made, k_refit_plan. */
+typedef enum { BVH_OVERLAP_BOXES = 0, BVH_OVERLAP_SELF = 1 } bvh_overlap_mode;
+int  bvh_overlap(bvh_ctx* ctx, const bvh_result* tree, const bvh_aabb* d_boxes, uint32_t n_boxes, int mode /* bvh_overlap_mode */,
+                 uint32_t* d_offsets /* u32[n_boxes + 1], device */, uint32_t* d_prims /* u32[capacity], device, or NULL: count only */,
+                 uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+
 /* ---- tree optimisation (no counterpart in the reference) ---------------------------------------------------------------------------------
  * Lower a built tree's SAH by treelet restructuring (Karras & Aila, HPG 2013): bottom-up, every treelet of 7 entries whose root holds enough leaves is replaced
  * by its SAH-optimal topology over the same entries.  The fast LBVH builds come out close to HPLOC quality; PLOC++ / HPLOC trees gain a few percent.
