@@ -282,6 +282,11 @@ class Context:
         self.device = device
         self._scenes = weakref.WeakSet()                  # bvh_scene objects bound to this ctx: destroyed before it
 
+    @property
+    def stream(self) -> int:
+        """bvh_ctx_stream: the hipStream_t the context enqueues on (the caller's own, if it was created on one)"""
+        return lib().bvh_ctx_stream(self.handle) or 0
+
     def set_profiling(self, level) -> None:
         """0 off, 1 stage events (reference Timer tokens), 2 + per-kernel events"""
         _check(lib().bvh_ctx_set_profiling(self.handle, int(level)), "bvh_ctx_set_profiling")
