@@ -35,10 +35,12 @@ INSTANCE = np.dtype([("object_to_world", "<f4", 12), ("blas", "<u4"), ("reserved
 INSTANCE_HIT = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4", 3)])   # bvh_instance_hit
 POINT_QUERY = np.dtype([("point", "<f4", 3), ("radius", "<f4")])                                               # bvh_point_query (bvh_closest_point)
 POINT_HIT = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("reserved", "<u4")])   # bvh_point_hit
+KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4")])                                                         # bvh_knn_hit (bvh_knn)
+KNN_MAX_K = 32
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
 TRANSFORMATION = np.dtype([("translation", "<f4", 3), ("pad", "<f4"), ("scale", "<f4", 3), ("pad1", "<f4"), ("quat", "<f4", 4), ("pad2", "<f4", 4)])
 assert RAY.itemsize == 32 and CAMERA.itemsize == 64 and TRANSFORMATION.itemsize == 64 and INSTANCE.itemsize == 64 and INSTANCE_HIT.itemsize == 32
-assert POINT_QUERY.itemsize == 16 and POINT_HIT.itemsize == 32
+assert POINT_QUERY.itemsize == 16 and POINT_HIT.itemsize == 32 and KNN_HIT.itemsize == 8
 
 
 def qt_rotation(axis_angle):
@@ -74,7 +76,7 @@ EXPORTS = [
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas",
-    "bvh_closest_point", "bvh_overlap",
+    "bvh_closest_point", "bvh_overlap", "bvh_knn",
 ]
 
 
@@ -204,6 +206,7 @@ def lib() -> C.CDLL:
         "bvh_scene_intersect": ([vp, vp, u32, vp, i32], i32),
         "bvh_scene_tlas": ([vp, C.POINTER(Result)], i32),
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
+        "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():
@@ -531,6 +534,50 @@ class _Builder:
             return hits.download(POINT_HIT, n_points)
         finally:
             hits.free()
+            if own is not None:
+                own.free()
+
+    def knn(self, points, k: int, radius=None, tris=None, vertices=None, indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64,
+            n_points: int | None = None):
+        """bvh_knn on this builder's tree: the ``k`` (1 .. KNN_MAX_K) nearest triangles within each query's radius.  ``points`` as for closest_point (a host
+        POINT_QUERY array, a host (n, 3) float array whose radius is ``radius`` (None: +inf), or a device buffer of POINT_QUERY records with ``n_points``).
+        Returns host arrays (hits KNN_HIT[n, k], counts u32[n]): hits[i, :counts[i]] is query i's list in ascending (dist2, prim) order, the slots past it
+        are {radius * radius, INVALID}.  Triangles as for intersect."""
+        if self._ctx is None:
+            raise BvhError("knn needs a built tree")
+        ctx = self._ctx
+        k = int(k)
+        if not 1 <= k <= KNN_MAX_K:
+            raise BvhError(f"k must be 1 .. {KNN_MAX_K}")
+        own = None
+        if isinstance(points, np.ndarray):
+            if points.dtype != POINT_QUERY:
+                xyz = np.asarray(points, dtype=np.float32)
+                if xyz.ndim != 2 or xyz.shape[1] != 3:
+                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
+                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
+                points["point"] = xyz
+                points["radius"] = np.float32(np.inf) if radius is None else np.float32(radius)
+            elif radius is not None:
+                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
+            n_points = points.shape[0]
+            own = points = ctx.upload(np.ascontiguousarray(points)) if n_points else None
+        elif n_points is None:
+            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
+            if n_points is None:
+                raise BvhError("n_points is required for device points")
+        inp = None
+        if tris is not None or vertices is not None or indices is not None:
+            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                             _ptr(indices) if indices is not None else None, n_vertices, 0)
+        hits = ctx.alloc(max(n_points * k, 1) * KNN_HIT.itemsize)
+        counts = ctx.alloc(max(n_points, 1) * 4)
+        try:
+            _check(lib().bvh_knn(ctx.handle, C.byref(self.result), C.byref(inp) if inp is not None else None,
+                                 _ptr(points) if points is not None else None, n_points, k, hits.ptr, counts.ptr), f"{ALGO_NAMES[self.ALGO]}::knn")
+            return hits.download(KNN_HIT, n_points * k).reshape(n_points, k), counts.download(np.uint32, n_points)
+        finally:
+            hits.free(); counts.free()
             if own is not None:
                 own.free()
 

@@ -194,7 +194,7 @@ void carve(bvh_ctx* c, char* base, uint32_t cap, size_t* total) {
     c->ploc.ids1 = k.take<u32>(n);
     c->ploc.status = k.take<u64>((size_t)PLOC_MAX_ITERS * ploc_chunks(cap));
     c->ploc.state = k.take<u32>(PLOC_STATE_WORDS);
-    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's / bvh_closest_point's overflow count (bvh_overlap: [58] count pass, [59] fill pass, [60..61] u64 total)
+    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's / bvh_closest_point's / bvh_knn's overflow count (bvh_overlap: [58] count pass, [59] fill pass, [60..61] u64 total)
     c->hploc.zero_parent = c->small + 1;
     c->overlap_sums = k.take<u64>(OVERLAP_SCAN_BLOCKS);
     *total = k.off;
@@ -387,7 +387,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); warm_knn(); }); }
     *out = c;
     return 0;
 }
@@ -822,6 +822,40 @@ int bvh_closest_point(bvh_ctx* c, const bvh_result* tree, const bvh_build_input*
     if (e == hipSuccess) {
         launch_closest_point(s, (int)tree->layout, query, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_points, n_points,
                              tree->d_nodes, tree->d_leaves, tree->n_leaves, tree->root, d_hits, overflow, c->parent);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
+    if (install.on) c->recorder.mark(s, nullptr);
+    return 0;
+}
+
+// ---- k-nearest queries (no counterpart in the reference) -------------------------------------------------------------------------------------------
+// bvh_closest_point's checks (query_check with the lists as the answer array) plus k's range, the list array's size and the third range; then its plan and
+// launch sequence
+int bvh_knn(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_point_query* d_points, uint32_t n_points, uint32_t k, bvh_knn_hit* d_hits,
+            uint32_t* d_counts) {
+    if (k == 0u || k > (uint32_t)BVH_KNN_MAX_K) return BVH_E_INVALID_ARG;
+    const uint64_t p_bytes = (uint64_t)n_points * sizeof(bvh_point_query), h_bytes = (uint64_t)n_points * k * sizeof(bvh_knn_hit);
+    if ((uint64_t)n_points * k >= (1ull << 32)) return BVH_E_INVALID_ARG;
+    bvh_build_input in;
+    int r = query_check(c, tree, tris, BVH_QUERY_CLOSEST, d_points, p_bytes, d_hits, h_bytes, &in);
+    if (r) return r;
+    if (d_counts && n_points) {                               // the third range: against the points and against the lists
+        const uintptr_t c0 = (uintptr_t)d_counts, c1 = c0 + (uint64_t)n_points * sizeof(u32);
+        const uintptr_t p0 = (uintptr_t)d_points, p1 = p0 + p_bytes, h0 = (uintptr_t)d_hits, h1 = h0 + h_bytes;
+        if ((c0 < p1 && p0 < c1) || (c0 < h1 && h0 < c1)) return BVH_E_INVALID_ARG;
+    }
+    if (n_points == 0) return 0;
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    query_plan(c, tree, s);
+    u32* overflow = c->small + 58;                            // queries left to the stackless pass (bvh_intersect's word: calls on one stream are ordered)
+    hipError_t e = hipMemsetAsync(overflow, 0, sizeof(u32), s);
+    if (e == hipSuccess) {
+        launch_knn(s, (int)tree->layout, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_points, n_points, k, tree->d_nodes,
+                   tree->d_leaves, tree->n_leaves, tree->root, d_hits, d_counts, overflow, c->parent);
         e = hipGetLastError();
     }
     if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }

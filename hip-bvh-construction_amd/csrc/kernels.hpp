@@ -168,6 +168,14 @@ void launch_closest_point(hipStream_t s, int layout, int query, int tri_format, 
                           uint32_t n_vertices, const void* d_points, uint32_t n_points, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root,
                           void* d_hits, uint32_t* d_overflow, const uint32_t* d_parent);
 
+// ---- k-nearest queries (knn.hip): bvh_knn's two kernels, arguments as launch_closest_point's (d_hits: bvh_knn_hit[n_points * k], query i's list at i * k;
+// d_counts: u32[n_points] or null; 1 <= k <= KNN_MAX_K).  k_knn (short stack, marks a query it leaves in d_hits[i * k].prim_idx) and k_knn_deep (stackless,
+// returns at once while *d_overflow == 0)
+constexpr int KNN_MAX_K = 32;                                // BVH_KNN_MAX_K (knn.hip asserts it): the largest list bucket
+void launch_knn(hipStream_t s, int layout, int tri_format, const void* d_tris, const void* d_vertices, const void* d_indices, uint32_t n_vertices,
+                const void* d_points, uint32_t n_points, uint32_t k, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root, void* d_hits,
+                uint32_t* d_counts, uint32_t* d_overflow, const uint32_t* d_parent);
+
 // ---- box queries (overlap.hip): bvh_overlap's kernels.  launch_overlap_count: k_overlap_count (short stack; d_offsets[i] = query i's count) + k_overlap_deep
 // (stackless, returns at once while *d_overflow == 0) + k_overlap_scan (two launches: the counts become u32[n_boxes + 1] offsets in place, saturated at
 // 0xFFFFFFFF, and *d_total the 64-bit total; d_sums: u64[OVERLAP_SCAN_BLOCKS] scratch).  launch_overlap_fill: k_overlap_fill + k_overlap_deep, which return at
@@ -226,6 +234,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn();
 
 } // namespace bvh

@@ -195,6 +195,12 @@ public:
               "closestPoint");
     }
 
+    // beyond the reference (bvh_knn): the k nearest triangles within each query's radius, as k (dist2, prim) records per query in ascending order (unused
+    // slots {r2, BVH_INVALID}) and, with d_counts, the lists' lengths; against the same tree and triangles as intersect
+    void knn(Context& context, const bvh_point_query* d_points, u32 n, u32 k, bvh_knn_hit* d_hits, u32* d_counts = nullptr) {
+        check(bvh_knn(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, d_points, n, k, d_hits, d_counts), "knn");
+    }
+
     // beyond the reference (bvh_overlap): which primitives' boxes each query box touches, as offsets + primitive indices; BVH_OVERLAP_SELF with the tree's own
     // primitive boxes gives every overlapping pair once.  d_prims NULL: count only.  Returns the total (the call waits for it)
     u64 overlap(Context& context, const bvh_aabb* d_boxes, u32 n, bvh_overlap_mode mode, u32* d_offsets, u32* d_prims, u64 capacity) {

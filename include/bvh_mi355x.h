@@ -241,6 +241,39 @@ int  bvh_intersect(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* 
 int  bvh_closest_point(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
                        const bvh_point_query* d_points, uint32_t n_points, bvh_point_hit* d_hits, int query /* bvh_query_kind */);
 
+/* ---- k-nearest queries (no counterpart in the reference) -------------------------------------------------------------------------------
+ * Which k triangles are nearest to each query point within its radius?  k (dist2, prim_idx) records per query: query i's list is d_hits[i*k .. i*k+k).
+ * Point-cloud normals, kNN graphs, particle neighbourhoods, Chamfer-style losses, robust ICP.
+ * tree / tris: exactly as bvh_closest_point — any bvh_result in either layout (a build's, a refit's, an optimised or a caller-filled one on the ctx's device),
+ * triangles in any bvh_tri_format (NULL: tree->d_tris is read as Triangle[n_leaves]); the same validation; arrays that are not a tree end in finite time.
+ * Candidate and acceptance are bvh_closest_point's, word for word: the candidate of a triangle is Ericson's ClosestPtPointTriangle in f32, operation for
+ * operation as stated there, dist2 = (dx*dx + dy*dy) + dz*dz; it is accepted iff dist2 <= r2, r2 = radius*radius in f32 (an infinite radius is no bound).
+ * Queries with a NaN coordinate, a NaN radius or radius < 0 are dead: they accept nothing.  A triangle with a NaN vertex is never accepted (its dist2 is NaN).
+ * Answer: query i's list is the min(k, accepted) accepted candidates with the smallest (dist2, prim_idx), compared lexicographically, stored in ascending
+ * order — it does not depend on the builder, the layout, the scheduler, the input format or the traversal order.  Slots past the list are
+ * {r2, BVH_INVALID}; for a dead query that is all k of them.  d_counts[i], when d_counts is given, is the list's length.
+ * With k == 1 the record equals (dist2, prim_idx) of bvh_closest_point BVH_QUERY_CLOSEST bit for bit, on every query.  A tree with fewer than k triangles is
+ * fine: the lists are short.
+ * Point clouds are served by degenerate triangles v1 == v2 == v3: region A of the formula then gives dist2 = |p - v1|^2 exactly as (dx*dx + dy*dy) + dz*dz
+ * with d = v1 - p, and prim_idx is the point's index.  BVH_TRI_PACKED36 (nine floats per point) is the cheap input for it.
+ * Box tests are bvh_closest_point's: every box grows on every axis by 2^-16 times its largest |coordinate|, its f32 squared distance to
+ * the point is lb, and the subtree is kept iff lb * (1 - 2^-20) <= the current bound: the dist2 of the list's last entry once the list holds k entries, r2
+ * before that.  The <= keeps a candidate of equal dist2 and smaller prim_idx reachable.  A query is well-conditioned when every entry of its true list
+ * satisfies §8e's condition: the f64 squared distance from the point to that triangle's box, grown by 2^-17 times its largest |coordinate|, is <= its dist2.
+ * The bound never drops below the true k-th dist2, so on such queries no ancestor of a true answer is culled and the list is exact.  On every query each
+ * reported entry is an accepted candidate of its prim with a bit-equal dist2, the entries are strictly ascending in (dist2, prim_idx), and no list is
+ * lexicographically below the true one.
+ * Errors (nothing is written or enqueued, BVH_E_INVALID_ARG): bvh_closest_point's (NULL ctx / tree / d_points / d_hits, n_leaves < 2, layout not 0 or 1, NULL
+ * d_nodes, layout 1 with NULL d_leaves, root not an internal node, no triangles or a tris format error, n_leaves larger than the ctx's capacity); k == 0 or
+ * k > BVH_KNN_MAX_K; the d_points / d_hits / d_counts ranges overlapping each other; n_points * k >= 2^32.  n_points == 0: 0, nothing is touched.
+ * Asynchronous on the ctx's stream, no read-back.  There is no depth limit: queries whose short stack would overflow are finished by a stackless pass through
+ * bvh_refit's parent plan, cached for the ctx's own tree as for bvh_intersect.  bvh_ctx_kernel_times reports k_knn, k_knn_deep and, when the plan is made,
+ * k_refit_plan. */
+#define BVH_KNN_MAX_K 32
+int  bvh_knn(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
+             const bvh_point_query* d_points, uint32_t n_points, uint32_t k, bvh_knn_hit* d_hits /* [n_points * k], query i's list at d_hits[i*k .. i*k+k) */,
+             uint32_t* d_counts /* [n_points] or NULL */);
+
 /* ---- box queries (no counterpart in the reference) -------------------------------------------------------------------------------------
  * Which primitives does each box touch?  The broad phase of collision detection, region selection, culling against an axis-aligned volume, neighbour gathering
  * on a bvh_build_boxes tree, "which instances does this volume touch" on a scene's top-level tree.
