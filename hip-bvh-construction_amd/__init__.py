@@ -76,7 +76,7 @@ EXPORTS = [
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas",
-    "bvh_closest_point", "bvh_overlap", "bvh_knn",
+    "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all",
 ]
 
 
@@ -114,6 +114,7 @@ TRI_PADDED64, TRI_PACKED36, TRI_INDEXED = 0, 1, 2
 QUERY_CLOSEST, QUERY_ANY = 0, 1      # bvh_query_kind
 _QUERY_IDS = {"closest": QUERY_CLOSEST, "any": QUERY_ANY}
 OVERLAP_BOXES, OVERLAP_SELF = 0, 1   # bvh_overlap_mode
+HITS_SORTED = 1                      # BVH_HITS_SORTED (bvh_intersect_all's flag)
 ABI_VERSION = 4                      # BVH_ABI_VERSION of include/bvh_mi355x.h this binding was written against
 # bvh_option (bvh_ctx_set_option) and the names this harness accepts for the values
 OPT_HPLOC_SCHEDULER, OPT_LBVH_SCHEDULER, OPT_SORT_TEST_KNOBS, OPT_PLOC_SCHEDULER = 0, 1, 2, 3
@@ -208,6 +209,7 @@ def lib() -> C.CDLL:
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_intersect_all": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -628,6 +630,62 @@ class _Builder:
             offsets.free()
             if prims is not None:
                 prims.free()
+            if own is not None:
+                own.free()
+
+    def intersect_all(self, rays, sorted: bool = True, count_only: bool = False, capacity: int | None = None, tris=None, vertices=None, indices=None,
+                      n_vertices: int = 0, tri_format: int = TRI_PADDED64, n: int | None = None):
+        """bvh_intersect_all on this builder's tree: every accepted hit along each ray.  ``rays`` a host RAY array or a device buffer (DeviceBuffer / int
+        address, with ``n``).  Returns host arrays (offsets u32[n + 1], hits HIT[total]): ray i's hits are hits[offsets[i]:offsets[i + 1]], in ascending
+        (t, prim) order when ``sorted`` (BVH_HITS_SORTED), in no particular order otherwise; an empty slice is a miss.  ``count_only`` returns offsets alone
+        (the crossing numbers in scanned form).  ``capacity`` None: a count-only call first, then a call with the exact capacity; a given capacity that is too
+        small is re-allocated with the total the call reported and the call repeated.  Triangles as for intersect."""
+        if self._ctx is None:
+            raise BvhError("intersect_all needs a built tree")
+        ctx = self._ctx
+        own = None
+        if isinstance(rays, np.ndarray):
+            if rays.dtype != RAY:
+                raise BvhError("rays must have dtype RAY (32-byte records)")
+            n = rays.shape[0]
+            own = rays = ctx.upload(np.ascontiguousarray(rays)) if n else None
+        elif n is None:
+            n = rays.nbytes // RAY.itemsize if isinstance(rays, DeviceBuffer) else None
+            if n is None:
+                raise BvhError("n is required for device rays")
+        if n == 0:                                        # no rays: the empty answer, without a call
+            off = np.zeros(1, dtype=np.uint32)
+            return off if count_only else (off, np.zeros(0, dtype=HIT))
+        inp = None
+        if tris is not None or vertices is not None or indices is not None:
+            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                             _ptr(indices) if indices is not None else None, n_vertices, 0)
+        p_inp = C.byref(inp) if inp is not None else None
+        flags = HITS_SORTED if sorted else 0
+        what = f"{ALGO_NAMES[self.ALGO]}::intersect_all"
+        offsets = ctx.alloc((n + 1) * 4)
+        hits = None
+        try:
+            total = C.c_uint64()
+            if count_only or capacity is None:
+                _check(lib().bvh_intersect_all(ctx.handle, C.byref(self.result), p_inp, _ptr(rays), n, flags, offsets.ptr, None, 0, C.byref(total)), what)
+                if count_only:
+                    return offsets.download(np.uint32, n + 1)
+                cap = total.value
+            else:
+                cap = int(capacity)
+            for _ in range(2):
+                hits = ctx.alloc(max(cap, 1) * HIT.itemsize)
+                _check(lib().bvh_intersect_all(ctx.handle, C.byref(self.result), p_inp, _ptr(rays), n, flags, offsets.ptr, hits.ptr, cap, C.byref(total)), what)
+                if total.value <= cap:
+                    break
+                hits.free(); hits = None
+                cap = total.value
+            return offsets.download(np.uint32, n + 1), hits.download(HIT, total.value)
+        finally:
+            offsets.free()
+            if hits is not None:
+                hits.free()
             if own is not None:
                 own.free()
 

@@ -198,7 +198,11 @@ void launch_overlap_count(hipStream_t s, int layout, int mode, const void* d_box
     using L0 = std::integral_constant<int, 0>; using L1 = std::integral_constant<int, 1>;
     auto by_mode = [&](auto L) { if (mode == BVH_OVERLAP_SELF) go(L, std::true_type{}); else go(L, std::false_type{}); };
     if (layout == 0) by_mode(L0{}); else by_mode(L1{});
-    // the scan: at most OVERLAP_SCAN_BLOCKS chunks of whole tiles over the n_boxes + 1 words
+    launch_overlap_scan(s, d_offsets, n_boxes, d_sums, d_total);
+}
+
+// the scan: at most OVERLAP_SCAN_BLOCKS chunks of whole tiles over the n_boxes + 1 words (bvh_intersect_all's counts go through it too: multihit.hip)
+void launch_overlap_scan(hipStream_t s, uint32_t* d_offsets, uint32_t n_boxes, uint64_t* d_sums, uint64_t* d_total) {
     const u64 words = (u64)n_boxes + 1ull, tiles = (words + SCAN_TILE - 1) / SCAN_TILE;
     const u64 tiles_per = (tiles + OVERLAP_SCAN_BLOCKS - 1) / OVERLAP_SCAN_BLOCKS;
     const u32 chunk = (u32)(tiles_per * SCAN_TILE), scan_blocks = (u32)((tiles + tiles_per - 1) / tiles_per);

@@ -213,6 +213,20 @@ public:
         check(bvh_overlap(context.handle(), &m_result, d_boxes, n, static_cast<int>(mode), d_offsets, d_prims, capacity, nullptr), "overlap");
     }
 
+    // beyond the reference (bvh_intersect_all): every accepted hit along each ray, as offsets + bvh_hit records (ascending (t, prim) per ray with
+    // BVH_HITS_SORTED in flags); against the same tree and triangles as intersect.  d_hits NULL: count only.  Returns the total (the call waits for it)
+    u64 intersectAll(Context& context, const bvh_ray* d_rays, u32 n, u32 flags, u32* d_offsets, bvh_hit* d_hits, u64 capacity) {
+        uint64_t total = 0;
+        check(bvh_intersect_all(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, d_rays, n, flags, d_offsets, d_hits, capacity,
+                                &total), "intersectAll");
+        return total;
+    }
+    // the asynchronous form: no read-back, the fill decides on the device whether the capacity suffices
+    void intersectAllAsync(Context& context, const bvh_ray* d_rays, u32 n, u32 flags, u32* d_offsets, bvh_hit* d_hits, u64 capacity) {
+        check(bvh_intersect_all(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, d_rays, n, flags, d_offsets, d_hits, capacity,
+                                nullptr), "intersectAll");
+    }
+
     // X::traverseBvh(Context&): GenerateRays -> the traversal kernel this builder's reference source selects -> RGBA read-back -> perf block.
     void traverseBvh(Context& context) {
         constexpr TraverseFlavour f = flavour<ALGO>();

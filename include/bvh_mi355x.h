@@ -211,6 +211,46 @@ typedef enum { BVH_QUERY_CLOSEST = 0, BVH_QUERY_ANY = 1 } bvh_query_kind;
 int  bvh_intersect(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
                    const bvh_ray* d_rays, uint32_t n_rays, bvh_hit* d_hits, int query /* bvh_query_kind */);
 
+/* ---- all-hits ray queries (no counterpart in the reference) ------------------------------------------------------------------------------
+ * Which triangles does each ray cross, ALL of them?  Transparency and alpha layers, thickness and path-length integrals, crossing-number inside / outside
+ * tests on closed meshes, CSG intervals, x-ray and attenuation renders, counting the shells a sensor ray passes through.  One call instead of re-issuing
+ * bvh_intersect with tmin moved past the last hit, which costs a descent per layer and loses hits that share a t.
+ * tree / tris: exactly as bvh_intersect — any bvh_result in either layout, read as it is (a build's, a refit's, an optimised or a caller-filled one on the
+ * ctx's device), triangles in any bvh_tri_format validated as by bvh_build_ex (NULL: tree->d_tris is read as Triangle[n_leaves]); nothing in the tree is
+ * written; a primitive or child index out of range is never followed, and arrays that are not a tree end in finite time with unspecified answers.
+ * Hit test and acceptance: bvh_intersect's, word for word — the reference's intersectTriangle in f32, operation for operation; a hit is accepted iff
+ * iu > 0 && iv > 0 && iw > 0 && tmin < it < tmax.  A ray with a NaN component, or with !(tmin < tmax), accepts nothing.
+ * Answer: ray i's set is ALL its accepted hits, as {it, iu, iv, prim_idx} records in compressed-row form: d_hits[d_offsets[i] .. d_offsets[i+1]) is ray i's
+ * slice, d_offsets[0] = 0, d_offsets[n_rays] = the total.  Each primitive appears at most once per slice.  There are no miss records: an empty slice is a
+ * miss.  With d_hits == NULL the call only counts: d_offsets is then the rays' crossing numbers in scanned form.
+ * Order inside a slice: without BVH_HITS_SORTED unspecified, but the same call on the same arrays gives the same bytes.  With BVH_HITS_SORTED each slice is in
+ * ascending (t, prim_idx) order, compared lexicographically; the whole d_hits array then does not depend on the builder, the layout, the scheduler, the
+ * triangle format or the traversal order.  Any other flag bit is an error.
+ * Box tests are bvh_intersect's conservative test (boxes grow by 2^-16 times their largest |coordinate|, slab interval ends widen by 2^-20
+ * relative) against [tmin, tmax] for the whole walk: the bound never shrinks.  §8b's argument needs only it < bound, which holds for every accepted hit, so on
+ * a well-conditioned ray (§8b's definition, unchanged: every accepted hit's point o + t*d lies in its triangle's box grown by half that growth) no ancestor of
+ * an accepted hit is culled and the set is exact.  On EVERY ray each reported record is an accepted hit of its primitive with bit-equal t / u / v, and the
+ * slice is a subset of the true set.
+ * Passes: the call always counts, then scans the counts into d_offsets, and keeps the 64-bit total in a device word.  It fills d_hits iff d_hits != NULL,
+ * total <= capacity and total < 2^32; that decision is made ON THE DEVICE (the fill launch reads the total word and returns at once), so the call stays
+ * asynchronous on the ctx's stream.  If the fill is skipped d_hits is not touched and d_offsets is still complete.  With total_out != NULL the call blocks on
+ * an 8-byte read-back into pinned words and stores the total; a host that guessed too small a capacity re-allocates and calls again.  A total of 2^32 or more
+ * saturates d_offsets at 0xFFFFFFFF; if total_out was given the call then returns BVH_E_TOO_LARGE (with *total_out set).  d_hits is never written outside
+ * ray i's slice, nor past the total.
+ * There is no depth limit: a ray whose short stack would overflow is finished by a stackless pass through bvh_refit's parent plan, cached for the ctx's own
+ * tree as for bvh_intersect and made per call for caller-owned arrays.  Count and fill agree on every ray's set whichever pass served it.
+ * Errors (nothing is written or enqueued, BVH_E_INVALID_ARG): bvh_intersect's (NULL ctx / tree / d_rays, n_leaves < 2, layout not 0 or 1, NULL d_nodes,
+ * layout 1 with NULL d_leaves, root not an internal node, no triangles or a tris format error, n_leaves larger than the ctx's capacity: call bvh_ctx_reserve
+ * first); NULL d_offsets; a flag bit other than BVH_HITS_SORTED; n_rays >= 2^30; d_offsets or d_hits (capacity records) overlapping d_rays or each other.
+ * n_rays == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.
+ * bvh_ctx_kernel_times reports k_hits_count, k_hits_deep (after each pass), k_overlap_scan (the scan is bvh_overlap's), k_hits_fill and, when the plan is
+ * made, k_refit_plan. */
+#define BVH_HITS_SORTED 1u
+int  bvh_intersect_all(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
+                       const bvh_ray* d_rays, uint32_t n_rays, uint32_t flags /* 0 or BVH_HITS_SORTED */,
+                       uint32_t* d_offsets /* u32[n_rays + 1], device */, bvh_hit* d_hits /* [capacity], device, or NULL: count only */,
+                       uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+
 /* ---- point queries (no counterpart in the reference) -----------------------------------------------------------------------------------
  * Which point of the mesh is nearest to each query point within its radius (BVH_QUERY_CLOSEST), or is any triangle within the radius (BVH_QUERY_ANY)?  One
  * bvh_point_hit per query: d_hits[i] answers d_points[i].  Unsigned distance fields, proximity tests, projection onto a surface, ICP correspondences.
