@@ -76,7 +76,7 @@ EXPORTS = [
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas",
-    "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all",
+    "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset",
 ]
 
 
@@ -198,6 +198,7 @@ def lib() -> C.CDLL:
         "bvh_abi_version": ([], u32), "bvh_abi_struct_sizes": ([C.POINTER(u32)], None),
         "bvh_refit": ([vp, C.POINTER(Result), vp, i32, C.POINTER(Timings)], i32),
         "bvh_refit_ex": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(Timings)], i32),
+        "bvh_refit_subset": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, C.POINTER(Timings)], i32),
         "bvh_intersect": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_optimize": ([vp, C.POINTER(Result), u32, C.POINTER(Timings)], i32),
         "bvh_build_boxes": ([vp, i32, vp, u32, i32, C.POINTER(Result), C.POINTER(Timings)], i32),
@@ -456,6 +457,37 @@ class _Builder:
         inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
                          _ptr(indices) if indices is not None else None, n_vertices, 0)
         _check(lib().bvh_refit_ex(self._ctx.handle, C.byref(self.result), C.byref(inp), C.byref(self.timings)), f"{ALGO_NAMES[self.ALGO]}::refit_ex")
+        return self._publish()
+
+    def refit_subset(self, prims, n_dirty: int | None = None, tris=None, vertices=None, indices=None, n_vertices: int = 0,
+                     tri_format: int = TRI_PADDED64) -> "_Builder":
+        """bvh_refit_subset: new boxes for the listed primitives' leaves and the paths from them to the root only.  ``prims``: the primitive indices whose
+        triangles changed — a numpy array (converted to u32 and uploaded for the call) or a device buffer of u32 (DeviceBuffer / int address, with ``n_dirty``).
+        Triangles: the COMPLETE arrays with the moved triangles updated in place, device inputs in ``tri_format`` as for refit_ex; none given: the tree's own
+        d_tris (Triangle[n]).  An upload through the context makes the next call renew the cached parent plan and leaf map: an animation loop keeps its list in
+        a DeviceBuffer."""
+        if self._ctx is None:
+            raise BvhError("refit_subset needs a built tree")
+        ctx = self._ctx
+        own = None
+        if isinstance(prims, np.ndarray):
+            host = np.ascontiguousarray(prims, dtype=np.uint32).ravel()
+            n_dirty = host.shape[0]
+            own = prims = ctx.upload(host)
+        elif n_dirty is None:
+            n_dirty = prims.nbytes // 4 if isinstance(prims, DeviceBuffer) else None
+            if n_dirty is None:
+                raise BvhError("n_dirty is required for device lists")
+        inp = None
+        if tris is not None or vertices is not None or indices is not None or tri_format != TRI_PADDED64:
+            inp = C.byref(BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                                     _ptr(indices) if indices is not None else None, n_vertices, 0))
+        try:
+            _check(lib().bvh_refit_subset(ctx.handle, C.byref(self.result), inp, _ptr(prims) or None, int(n_dirty), C.byref(self.timings)),
+                   f"{ALGO_NAMES[self.ALGO]}::refit_subset")
+        finally:
+            if own is not None:
+                own.free()                                # (hipFree waits for the kernels that read it)
         return self._publish()
 
     def optimize(self, rounds: int = 3) -> "_Builder":

@@ -86,6 +86,16 @@ struct bvh_ctx {
     // {plan_serial == tree_serial, plan_n, plan_root}.  plan_serial 0: no plan (a refit of caller-owned arrays made one of ITS tree in `parent`).
     uint64_t tree_serial = 1, plan_serial = 0;
     uint32_t plan_n = 0, plan_root = 0;
+    // bvh_refit_subset's words, outside the arena (a build's footprint and the emitters' scratch protocols do not change): leaf_of_prim | owner | pending, u32[subset_cap]
+    // each, allocated by the first bvh_refit_subset and again after the capacity grew.  owner / pending are zeroed once and kept all-zero by a completed call;
+    // subset_dirty: set while a call is being enqueued and left set by a call on caller-owned arrays (not a tree: marks can stay behind); the next call zeroes
+    // the words first, whichever tree it is on (as scratch_dirty).  The leaf map of the
+    // ctx's own tree is kept under the plan's rule: valid for {map_serial == tree_serial, map_n, map_root}; bvh_optimize moves no leaf and leaves it valid.
+    u32* subset_words = nullptr;
+    uint32_t subset_cap = 0;
+    bool subset_dirty = false;
+    uint64_t map_serial = 0;
+    uint32_t map_n = 0, map_root = 0;
 };
 
 // bvh_scene: device memory of its own (one allocation, carved as below), outside the ctx's arena; only the top-level build uses the arena
@@ -387,7 +397,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); }); }
     *out = c;
     return 0;
 }
@@ -399,6 +409,7 @@ void bvh_ctx_destroy(bvh_ctx* c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->arena) hipFree(c->arena);
     if (c->tris) hipFree(c->tris);
+    if (c->subset_words) hipFree(c->subset_words);
     for (auto& e : c->ev) if (e) hipEventDestroy(e);
     if (c->h_pinned) hipHostFree(c->h_pinned);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -754,6 +765,87 @@ int bvh_refit_ex(bvh_ctx* c, bvh_result* io, const bvh_build_input* in, bvh_timi
     r = stage_extents_valid(in); if (r) return r;
     Bind b(c->device);
     return refit_impl(c, io, in, tm);
+}
+
+// ---- partial refit (no counterpart in the reference) --------------------------------------------------------------------------------------------
+// the words of bvh_refit_subset, sized by the ctx's capacity.  The new block is allocated before the old one is released: a failed allocation changes nothing
+static int ensure_subset_words(bvh_ctx* c) {
+    if (c->subset_words && c->subset_cap == c->cap) return 0;
+    u32* p = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), (size_t)c->cap * 3 * sizeof(u32)));
+    if (c->subset_words) {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipFree(c->subset_words);
+        if (e != hipSuccess) { (void)hipFree(p); return -(int)e; }
+    }
+    c->subset_words = p; c->subset_cap = c->cap; c->map_serial = 0;
+    c->subset_dirty = true;                                   // (zeroed by the call that follows, on the ctx's stream)
+    return 0;
+}
+
+// Checked before anything is enqueued: an error changes nothing.  Then: the parent plan and the leaf map unless the ctx's own tree has them, the box pass over the
+// list, mark + climb.  Timings: ms_extents = the box pass, ms_build = plan + map + mark + climb (bvh_ctx_kernel_times names them apart)
+int bvh_refit_subset(bvh_ctx* c, bvh_result* io, const bvh_build_input* in, const uint32_t* d_prims, uint32_t n_dirty, bvh_timings* tm) {
+    int r = refit_check(c, io); if (r) return r;
+    bvh_build_input inp; std::memset(&inp, 0, sizeof inp);
+    if (in) { r = stage_extents_valid(in); if (r) return r; inp = *in; }
+    else { if (!io->d_tris) return BVH_E_INVALID_ARG; inp.tri_format = BVH_TRI_PADDED64; inp.d_tris = io->d_tris; }
+    if ((n_dirty && !d_prims) || n_dirty >= (1u << 30)) return BVH_E_INVALID_ARG;
+    const uint32_t n = io->n_leaves;
+    {   // the list may not overlap what the call writes
+        const uintptr_t p0 = (uintptr_t)d_prims, p1 = p0 + (uint64_t)n_dirty * sizeof(u32);
+        auto overlaps = [&](const void* a, uint64_t bytes) { const uintptr_t a0 = (uintptr_t)a; return a && n_dirty && p0 < a0 + bytes && a0 < p1; };
+        if (overlaps(io->d_prim_aabbs, (uint64_t)n * sizeof(bvh_aabb)) || overlaps(io->d_scene_extent, sizeof(bvh_aabb)) ||
+            overlaps(io->d_nodes, (uint64_t)(io->layout == 0 ? 2 * (uint64_t)n - 1 : n - 1) * sizeof(bvh2_node)) ||
+            (io->layout == 1 && overlaps(io->d_leaves, (uint64_t)n * sizeof(bvh_primref))) || overlaps(c->parent, (uint64_t)c->cap * 2 * sizeof(u32)) ||
+            overlaps(c->subset_words, (uint64_t)c->subset_cap * 3 * sizeof(u32))) return BVH_E_INVALID_ARG;
+    }
+    if (n_dirty == 0) return 0;
+    Bind b(c->device);
+    r = ensure_subset_words(c); if (r) return r;
+    hipStream_t s = c->stream;
+    u32* const leaf_of_prim = c->subset_words; u32* const owner = leaf_of_prim + c->subset_cap; u32* const pending = owner + c->subset_cap;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    const bool prof = c->profiling && sampled;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    const bool own = io->d_nodes == c->nodes;
+    // caller-owned arrays may be anything: arrays that are not a tree can leave marks behind, so the call after one of theirs starts from zeroed words
+    if (c->subset_dirty) HIP_TRY(hipMemsetAsync(owner, 0, (size_t)c->subset_cap * 2 * sizeof(u32), s));
+    c->subset_dirty = true;
+    if (prof) HIP_TRY(hipEventRecord(c->ev[0], s));
+    if (!own || c->plan_serial != c->tree_serial || c->plan_n != n || c->plan_root != io->root) {
+        launch_refit_plan(s, io->d_nodes, n, io->root, c->parent);
+        c->plan_serial = own ? c->tree_serial : 0; c->plan_n = n; c->plan_root = io->root;
+    }
+    if (!own || c->map_serial != c->tree_serial || c->map_n != n || c->map_root != io->root) {
+        launch_refit_leafmap(s, io->d_nodes, io->d_leaves, (int)io->layout, n, leaf_of_prim);
+        c->map_serial = own ? c->tree_serial : 0; c->map_n = n; c->map_root = io->root;
+    }
+    if (prof) HIP_TRY(hipEventRecord(c->ev[1], s));
+    launch_refit_subset_boxes(s, (int)inp.tri_format, inp.d_tris, inp.d_vertices, inp.d_indices, inp.n_vertices, d_prims, n_dirty, leaf_of_prim, owner,
+                              io->d_prim_aabbs, io->d_nodes, io->d_leaves, (int)io->layout, n);
+    if (prof) HIP_TRY(hipEventRecord(c->ev[2], s));
+    launch_refit_subset_climb(s, d_prims, n_dirty, leaf_of_prim, owner, pending, c->parent, io->d_prim_aabbs, io->d_nodes, io->d_leaves, (int)io->layout, n, io->root,
+                              io->d_scene_extent);
+    { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { c->plan_serial = 0; c->map_serial = 0; return -(int)e; } }
+    c->subset_dirty = !own;                                   // (marks that caller-owned arrays left behind never reach the next call, whoever's tree it is on)
+    if (install.on) c->recorder.mark(s, nullptr);
+    if (prof) HIP_TRY(hipEventRecord(c->ev[4], s));
+    io->d_tris = inp.tri_format == BVH_TRI_INDEXED ? inp.d_vertices : inp.d_tris;
+    if (tm) {
+        std::memset(tm, 0, sizeof *tm);
+        tm->sampled = prof ? 1u : 0u;
+        if (prof) {
+            float ms_plan = 0.f, ms_climb = 0.f;
+            HIP_TRY(hipEventSynchronize(c->ev[4]));
+            HIP_TRY(hipEventElapsedTime(&ms_plan, c->ev[0], c->ev[1]));
+            HIP_TRY(hipEventElapsedTime(&tm->ms_extents, c->ev[1], c->ev[2]));
+            HIP_TRY(hipEventElapsedTime(&ms_climb, c->ev[2], c->ev[4]));
+            tm->ms_build = ms_plan + ms_climb;
+            tm->ms_total = tm->ms_extents + tm->ms_build;
+        }
+    }
+    return 0;
 }
 
 // ---- ray queries (no counterpart in the reference) ----------------------------------------------------------------------------------------------

@@ -150,6 +150,31 @@ __device__ __forceinline__ Box tri_box_gather(const float4* t) {
     return { clamp_lo_reset(fminf(fminf(a.x, a.w), b.z)), clamp_lo_reset(fminf(fminf(a.y, b.x), b.w)), clamp_lo_reset(fminf(fminf(a.z, b.y), c)),
              clamp_hi_reset(fmaxf(fmaxf(a.x, a.w), b.z)), clamp_hi_reset(fmaxf(fmaxf(a.y, b.x), b.w)), clamp_hi_reset(fmaxf(fmaxf(a.z, b.y), c)) };
 }
+// Stage E's box of one triangle, the expression itself (stage_em.hip's k_extents* and refit_subset.hip's box pass share it, so their bits cannot differ): Aabb()
+// is the reset box and grow() is fminf / fmaxf (src/Common.h:327-345), so an axis whose three coordinates are all NaN — or all +inf — keeps +-FltMax.  Only for
+// translation units compiled WITHOUT -fno-honor-nans (Makefile): the emit kernels use tri_box_gather above.
+__device__ __forceinline__ Box stage_e_box(float x0, float y0, float z0, float x1, float y1, float z1, float x2, float y2, float z2) {
+    Box bx;
+    bx.lx = fminf(FMAX, fminf(fminf(x0, x1), x2)); bx.ly = fminf(FMAX, fminf(fminf(y0, y1), y2)); bx.lz = fminf(FMAX, fminf(fminf(z0, z1), z2));
+    bx.hx = fmaxf(-FMAX, fmaxf(fmaxf(x0, x1), x2)); bx.hy = fmaxf(-FMAX, fmaxf(fmaxf(y0, y1), y2)); bx.hz = fmaxf(-FMAX, fmaxf(fmaxf(z0, z1), z2));
+    return bx;
+}
+// ... of 64-byte Triangle record i: 2 x 16 B + 1 x 4 B, no lane touches the 28 bytes of padding;  v1 = (a.x,a.y,a.z)  v2 = (a.w,b.x,b.y)  v3 = (b.z,b.w,c)
+__device__ __forceinline__ Box stage_e_box_padded(const float4* __restrict__ tris, u32 i) {
+    const float4 a = tris[(size_t)i * 4 + 0];
+    const float4 b = tris[(size_t)i * 4 + 1];
+    const float  c = reinterpret_cast<const float*>(tris + (size_t)i * 4 + 2)[0];
+    return stage_e_box(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c);
+}
+// ... of nine consecutive floats (a PACKED36 record, in LDS or in memory)
+__device__ __forceinline__ Box stage_e_box9(const float* t) { return stage_e_box(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8]); }
+// ... of INDEXED triangle i: an index >= n_verts reads vertex 0 (never out of bounds)
+__device__ __forceinline__ Box stage_e_box_indexed(const float* __restrict__ verts, const u32* __restrict__ idx, u32 n_verts, u32 i) {
+    u32 i0 = idx[(size_t)i * 3 + 0], i1 = idx[(size_t)i * 3 + 1], i2 = idx[(size_t)i * 3 + 2];
+    if (i0 >= n_verts) i0 = 0; if (i1 >= n_verts) i1 = 0; if (i2 >= n_verts) i2 = 0;
+    const float* a = verts + (size_t)i0 * 3; const float* b = verts + (size_t)i1 * 3; const float* c = verts + (size_t)i2 * 3;
+    return stage_e_box(a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]);
+}
 __device__ __forceinline__ Box box_load_u(const bvh_aabb* p) {
     const float* f = reinterpret_cast<const float*>(p);
     return { f[0], f[1], f[2], f[3], f[4], f[5] };

@@ -151,6 +151,19 @@ void ploc_enqueue(hipStream_t s, const PlocScratch& sc, uint32_t n, void* d_node
 void launch_refit_plan(hipStream_t s, const void* d_nodes, uint32_t n, uint32_t root, uint32_t* d_parent);
 void launch_refit_climb(hipStream_t s, const void* d_prim_boxes, void* d_nodes, void* d_leaves, int layout, uint32_t n, const uint32_t* d_parent, uint32_t* d_flags);
 
+// ---- partial refit (refit_subset.hip): bvh_refit_subset's kernels.  d_leaf_of_prim: u32[n], the leaf (sorted position) that holds each primitive, INVALID where none
+// does — launch_refit_leafmap makes it from the leaf records.  d_owner: u32[n] per leaf, d_pending: u32[n-1] per internal node, all-zero before the launches and
+// left so.  launch_refit_subset_boxes: k_refit_subset_boxes (claims each listed leaf once, stage E's box of its triangle into d_prim_boxes and the leaf record);
+// launch_refit_subset_climb: k_refit_subset_mark + k_refit_subset_climb (the boxes of the ancestors, the root's box into d_scene).  Triangles: a validated
+// bvh_build_input's fields, parent: the plan of launch_refit_plan
+void launch_refit_leafmap(hipStream_t s, const void* d_nodes, const void* d_leaves, int layout, uint32_t n, uint32_t* d_leaf_of_prim);
+void launch_refit_subset_boxes(hipStream_t s, int tri_format, const void* d_tris, const void* d_vertices, const void* d_indices, uint32_t n_vertices,
+                               const uint32_t* d_prims, uint32_t n_dirty, const uint32_t* d_leaf_of_prim, uint32_t* d_owner, void* d_prim_boxes, void* d_nodes,
+                               void* d_leaves, int layout, uint32_t n);
+void launch_refit_subset_climb(hipStream_t s, const uint32_t* d_prims, uint32_t n_dirty, const uint32_t* d_leaf_of_prim, uint32_t* d_owner, uint32_t* d_pending,
+                               const uint32_t* d_parent, const void* d_prim_boxes, void* d_nodes, const void* d_leaves, int layout, uint32_t n, uint32_t root,
+                               void* d_scene);
+
 // ---- tree optimisation (optimize.hip): one round of bvh_optimize's treelet restructuring (treelet roots: nodes with >= gamma leaves).  d_parent: the plan of
 // launch_refit_plan, kept right (the rebuild rewrites the parents of what it moves); d_flags: u32[n-1] exchange words, all-INVALID before the launch and left so
 void launch_optimize(hipStream_t s, void* d_nodes, const void* d_leaves, int layout, uint32_t n, uint32_t gamma, uint32_t* d_parent, uint32_t* d_flags);
@@ -247,6 +260,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit();
 
 } // namespace bvh

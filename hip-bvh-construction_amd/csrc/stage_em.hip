@@ -73,15 +73,10 @@ __global__ __launch_bounds__(EX_BLOCK) void k_extents(const float4* __restrict__
     Box acc = box_empty();
     const u32 stride = gridDim.x * EX_BLOCK;
     for (u32 i = blockIdx.x * EX_BLOCK + threadIdx.x; i < n; i += stride) {
-        const float4 a = tris[(size_t)i * 4 + 0];
-        const float4 b = tris[(size_t)i * 4 + 1];
-        const float  c = reinterpret_cast<const float*>(tris + (size_t)i * 4 + 2)[0];
-        // v1 = (a.x,a.y,a.z)  v2 = (a.w,b.x,b.y)  v3 = (b.z,b.w,c)
-        Box bx;
         // (Aabb() is the reset box and grow() is fminf / fmaxf, src/Common.h:327-345: a triangle whose three coordinates on an axis are all NaN — or all +inf — keeps
-        // +-FltMax there; tests/test_gpu_round5.py ff_filled_triangle found the difference against the reference's kernel)
-        bx.lx = fminf(FMAX, fminf(fminf(a.x, a.w), b.z)); bx.ly = fminf(FMAX, fminf(fminf(a.y, b.x), b.w)); bx.lz = fminf(FMAX, fminf(fminf(a.z, b.y), c));
-        bx.hx = fmaxf(-FMAX, fmaxf(fmaxf(a.x, a.w), b.z)); bx.hy = fmaxf(-FMAX, fmaxf(fmaxf(a.y, b.x), b.w)); bx.hz = fmaxf(-FMAX, fmaxf(fmaxf(a.z, b.y), c));
+        // +-FltMax there; tests/test_gpu_round5.py ff_filled_triangle found the difference against the reference's kernel.  common.hpp stage_e_box: shared with
+        // bvh_refit_subset's box pass)
+        const Box bx = stage_e_box_padded(tris, i);
         box_store(boxes + i, bx);
         acc = box_union(acc, bx);
     }
@@ -106,10 +101,7 @@ __global__ __launch_bounds__(EM_BLOCK) void k_extents_packed(const float* __rest
         for (u32 k = vecs * 4u + threadIdx.x; k < words; k += EM_BLOCK) s_t[k] = src[k];
         __syncthreads();
         if (threadIdx.x < cnt) {
-            const float* t = s_t + threadIdx.x * 9;
-            Box bx;
-            bx.lx = fminf(FMAX, fminf(fminf(t[0], t[3]), t[6])); bx.ly = fminf(FMAX, fminf(fminf(t[1], t[4]), t[7])); bx.lz = fminf(FMAX, fminf(fminf(t[2], t[5]), t[8]));
-            bx.hx = fmaxf(-FMAX, fmaxf(fmaxf(t[0], t[3]), t[6])); bx.hy = fmaxf(-FMAX, fmaxf(fmaxf(t[1], t[4]), t[7])); bx.hz = fmaxf(-FMAX, fmaxf(fmaxf(t[2], t[5]), t[8]));
+            const Box bx = stage_e_box9(s_t + threadIdx.x * 9);
             box_store(boxes + base + threadIdx.x, bx);
             acc = box_union(acc, bx);
         }
@@ -125,12 +117,7 @@ __global__ __launch_bounds__(EX_BLOCK) void k_extents_indexed(const float* __res
     Box acc = box_empty();
     const u32 stride = gridDim.x * EX_BLOCK;
     for (u32 i = blockIdx.x * EX_BLOCK + threadIdx.x; i < n; i += stride) {
-        u32 i0 = idx[(size_t)i * 3 + 0], i1 = idx[(size_t)i * 3 + 1], i2 = idx[(size_t)i * 3 + 2];
-        if (i0 >= n_verts) i0 = 0; if (i1 >= n_verts) i1 = 0; if (i2 >= n_verts) i2 = 0;   // never read out of bounds
-        const float* a = verts + (size_t)i0 * 3; const float* b = verts + (size_t)i1 * 3; const float* c = verts + (size_t)i2 * 3;
-        Box bx;
-        bx.lx = fminf(FMAX, fminf(fminf(a[0], b[0]), c[0])); bx.ly = fminf(FMAX, fminf(fminf(a[1], b[1]), c[1])); bx.lz = fminf(FMAX, fminf(fminf(a[2], b[2]), c[2]));
-        bx.hx = fmaxf(-FMAX, fmaxf(fmaxf(a[0], b[0]), c[0])); bx.hy = fmaxf(-FMAX, fmaxf(fmaxf(a[1], b[1]), c[1])); bx.hz = fmaxf(-FMAX, fmaxf(fmaxf(a[2], b[2]), c[2]));
+        const Box bx = stage_e_box_indexed(verts, idx, n_verts, i);                       // (an index >= n_verts reads vertex 0: never out of bounds)
         box_store(boxes + i, bx);
         acc = box_union(acc, bx);
     }

@@ -174,6 +174,24 @@ public:
         publish(context, r, t, r.n_leaves);
     }
 
+    // beyond the reference (bvh_refit_subset): only the listed triangles of `primitives` moved — their leaves and the paths from them to the root get new boxes,
+    // the rest of the tree is not touched; then the tail of build() (collapse + m_cost) as after a build.  The triangles and the list are copied into device
+    // arrays the builder owns (d_subsetTriangles / d_subsetList); a host whose data is on the device already calls bvh_refit_subset itself
+    void refitSubset(Context& context, std::vector<Triangle>& primitives, const std::vector<u32>& dirty) {
+        if (static_cast<u32>(primitives.size()) != m_result.n_leaves) throw std::runtime_error("refitSubset: triangle count differs from the built tree's");
+        bvh_ctx* c = context.handle();
+        d_subsetTriangles.resize(c, primitives.size()); d_subsetList.resize(c, dirty.empty() ? 1 : dirty.size());
+        check(bvh_dev_upload(c, d_subsetTriangles.ptr(), primitives.data(), primitives.size() * sizeof(Triangle)), "bvh_dev_upload");
+        if (!dirty.empty()) check(bvh_dev_upload(c, d_subsetList.ptr(), dirty.data(), dirty.size() * sizeof(u32)), "bvh_dev_upload");
+        bvh_build_input in{}; in.tri_format = BVH_TRI_PADDED64; in.morton_bits = 30; in.d_tris = d_subsetTriangles.ptr();
+        bvh_timings t{};
+        check(bvh_refit_subset(c, &m_result, &in, d_subsetList.ptr(), static_cast<u32>(dirty.size()), &t), "refitSubset");
+        m_result.d_tris = d_subsetTriangles.ptr();            // (also after an empty list, which touches nothing: the triangles are the caller's new ones)
+        m_triFormat = BVH_TRI_PADDED64;
+        const bvh_result r = m_result;
+        publish(context, r, t, r.n_leaves);
+    }
+
     // beyond the reference (bvh_optimize): lower the SAH of the tree built (or refit) last by treelet restructuring, in place; then the tail of build()
     // (collapse + m_cost) as after a build
     void optimize(Context& context, u32 rounds = 3) {
@@ -319,6 +337,7 @@ public:
     float m_costBvh2 = 0.0f;             // BVH2 SAH (Utility::calculateLbvhCost formula)
     u32 m_nWideNodes = 0;                // wide nodes of the collapsed tree (root 0)
     DeviceArray<Bvh4Node> d_wideBvhNodes; DeviceArray<PrimNode> d_wideLeafNodes;      // locals of the reference's build(), kept here
+    DeviceArray<Triangle> d_subsetTriangles; DeviceArray<u32> d_subsetList;             // refitSubset's device copies (m_result.d_tris points at the first)
     DeviceArray<Ray> d_rayBuffer; DeviceArray<u32> d_rayCounterBuffer; DeviceArray<u8> d_colorBuffer; DeviceArray<Bvh2Node> d_lbvhLayoutNodes;
     std::vector<u8> m_colorBuffer; u32 m_width = 0, m_height = 0;                      // the image traverseBvh() rendered (RGBA8)
     bvh_result m_result{};

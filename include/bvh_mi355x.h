@@ -181,6 +181,28 @@ int  bvh_sort_pairs64(bvh_ctx* ctx, const uint64_t* d_keys_in, const uint32_t* d
 int  bvh_refit(bvh_ctx* ctx, bvh_result* io, const void* tris, int tris_on_device, bvh_timings* timings /* may be NULL */);
 /* the same on any bvh_tri_format (morton_bits is ignored) */
 int  bvh_refit_ex(bvh_ctx* ctx, bvh_result* io, const bvh_build_input* in, bvh_timings* timings /* may be NULL */);
+/* Partial refit: new boxes for the listed primitives' leaves and for the nodes on the paths from those leaves to the root — nothing else is written, and the work
+ * is bounded by n_dirty x depth (a few moved triangles in a large static tree).  io: any tree bvh_refit accepts, either layout.  in: the COMPLETE triangle arrays with
+ * the moved triangles already updated in place, any bvh_tri_format, validated as by bvh_refit_ex (NULL: io->d_tris is Triangle[n_leaves]).  d_prims: device array of
+ * the primitive indices whose triangles changed; duplicates are allowed in any number, an index >= n_leaves is ignored.
+ * For every distinct listed primitive p: d_prim_aabbs[p] and the box of the leaf record that holds p become the box stage E writes for triangle p (bit-identical,
+ * NaN / infinity clamping included; a primitive no leaf holds gets only its d_prim_aabbs entry).  Every internal node on a path from such a leaf to the root gets the
+ * componentwise fminf / fmaxf union of its two children's boxes as they are after the call: a child off every dirty path contributes the box it stores — it is read,
+ * never recomputed.  d_scene_extent becomes the root's new box; io->d_tris is set as by bvh_refit_ex.  NOT written: node and leaf records off every dirty path,
+ * d_prim_aabbs of unlisted primitives, child links, leaf prim indices, root, d_sorted_*, d_morton_keys.
+ * If every unlisted triangle of `in` yields the box already stored for it, all arrays compare equal to those after bvh_refit_ex(ctx, io, in) (byte-identical when no
+ * coordinate is a zero of mixed sign).  Arrays that are not a tree: the call ends in finite time with unspecified boxes and writes nothing outside the arrays.
+ * The parent plan and the leaf map (which leaf holds which primitive) of the ctx's own tree are made once and kept as bvh_refit's plan is — bvh_optimize keeps
+ * both valid —, caller-owned arrays get new ones on every call, and the call after one on caller-owned arrays first zeroes 8 bytes
+ * per primitive of capacity: on caller-owned arrays the call costs O(capacity), not O(n_dirty x depth).  The first call on a ctx (and the first after its capacity grew) allocates 12 bytes per primitive
+ * of capacity outside the arena; if that fails the HIP error is returned and nothing has changed.
+ * timings: ms_extents = the box pass, ms_build = plan + map + mark + climb, sampling rules of a build.  bvh_ctx_kernel_times reports k_refit_subset_boxes /
+ * k_refit_subset_mark / k_refit_subset_climb and, when they run, k_refit_plan / k_refit_leafmap.  Above some dirty fraction bvh_refit is the faster
+ * call; where that lies has not been measured yet (tools/time_refit_subset.py writes it to profiles/refit_subset.md).
+ * Errors (nothing is written or enqueued): those of bvh_refit_ex, NULL d_prims with n_dirty > 0, n_dirty >= 2^30, d_prims overlapping an array the call writes:
+ * BVH_E_INVALID_ARG.  n_dirty == 0 returns 0 and touches nothing.  Asynchronous on the ctx's stream, except for what the timings need. */
+int  bvh_refit_subset(bvh_ctx* ctx, bvh_result* io, const bvh_build_input* in /* NULL: io->d_tris is Triangle[n_leaves] */,
+                      const uint32_t* d_prims /* device, [n_dirty] */, uint32_t n_dirty, bvh_timings* timings /* may be NULL */);
 
 /* ---- ray queries (no counterpart in the reference) -----------------------------------------------------------------------------------
  * Which triangle does each ray hit first (BVH_QUERY_CLOSEST), or does it hit any (BVH_QUERY_ANY)?  One bvh_hit per ray: d_hits[i] answers d_rays[i].
