@@ -76,7 +76,7 @@ EXPORTS = [
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas",
-    "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset",
+    "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
 ]
 
 
@@ -115,6 +115,7 @@ QUERY_CLOSEST, QUERY_ANY = 0, 1      # bvh_query_kind
 _QUERY_IDS = {"closest": QUERY_CLOSEST, "any": QUERY_ANY}
 OVERLAP_BOXES, OVERLAP_SELF = 0, 1   # bvh_overlap_mode
 HITS_SORTED = 1                      # BVH_HITS_SORTED (bvh_intersect_all's flag)
+RADIUS_SORTED = 1                    # BVH_RADIUS_SORTED (bvh_radius_search's flag)
 ABI_VERSION = 4                      # BVH_ABI_VERSION of include/bvh_mi355x.h this binding was written against
 # bvh_option (bvh_ctx_set_option) and the names this harness accepts for the values
 OPT_HPLOC_SCHEDULER, OPT_LBVH_SCHEDULER, OPT_SORT_TEST_KNOBS, OPT_PLOC_SCHEDULER = 0, 1, 2, 3
@@ -211,6 +212,7 @@ def lib() -> C.CDLL:
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_intersect_all": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_radius_search": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -714,6 +716,71 @@ class _Builder:
                 hits.free(); hits = None
                 cap = total.value
             return offsets.download(np.uint32, n + 1), hits.download(HIT, total.value)
+        finally:
+            offsets.free()
+            if hits is not None:
+                hits.free()
+            if own is not None:
+                own.free()
+
+    def radius_search(self, points, radius=None, sorted: bool = True, count_only: bool = False, capacity: int | None = None, tris=None, vertices=None,
+                      indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64, n_points: int | None = None):
+        """bvh_radius_search on this builder's tree: every triangle within each query's radius.  ``points`` as for closest_point (a host POINT_QUERY array, a
+        host (n, 3) float array whose radius is ``radius`` (a scalar or an array of n; None: +inf), or a device buffer of POINT_QUERY records with ``n_points``).
+        Returns host arrays (offsets u32[n + 1], hits KNN_HIT[total]): query i's neighbours are hits[offsets[i]:offsets[i + 1]], in ascending (dist2, prim)
+        order when ``sorted`` (BVH_RADIUS_SORTED), in no particular order otherwise; an empty slice is "nothing within the radius".  ``count_only`` returns
+        offsets alone (the neighbour counts in scanned form).  ``capacity`` None: a count-only call first, then a call with the exact capacity; a given
+        capacity that is too small is re-allocated with the total the call reported and the call repeated.  Triangles as for intersect."""
+        if self._ctx is None:
+            raise BvhError("radius_search needs a built tree")
+        ctx = self._ctx
+        own = None
+        if isinstance(points, np.ndarray):
+            if points.dtype != POINT_QUERY:
+                xyz = np.asarray(points, dtype=np.float32)
+                if xyz.ndim != 2 or xyz.shape[1] != 3:
+                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
+                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
+                points["point"] = xyz
+                points["radius"] = np.float32(np.inf) if radius is None else np.asarray(radius, dtype=np.float32)
+            elif radius is not None:
+                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
+            n_points = points.shape[0]
+            own = points = ctx.upload(np.ascontiguousarray(points)) if n_points else None
+        elif n_points is None:
+            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
+            if n_points is None:
+                raise BvhError("n_points is required for device points")
+        n = n_points
+        if n == 0:                                        # no queries: the empty answer, without a call
+            off = np.zeros(1, dtype=np.uint32)
+            return off if count_only else (off, np.zeros(0, dtype=KNN_HIT))
+        inp = None
+        if tris is not None or vertices is not None or indices is not None:
+            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                             _ptr(indices) if indices is not None else None, n_vertices, 0)
+        p_inp = C.byref(inp) if inp is not None else None
+        flags = RADIUS_SORTED if sorted else 0
+        what = f"{ALGO_NAMES[self.ALGO]}::radius_search"
+        offsets = ctx.alloc((n + 1) * 4)
+        hits = None
+        try:
+            total = C.c_uint64()
+            if count_only or capacity is None:
+                _check(lib().bvh_radius_search(ctx.handle, C.byref(self.result), p_inp, _ptr(points), n, flags, offsets.ptr, None, 0, C.byref(total)), what)
+                if count_only:
+                    return offsets.download(np.uint32, n + 1)
+                cap = total.value
+            else:
+                cap = int(capacity)
+            for _ in range(2):
+                hits = ctx.alloc(max(cap, 1) * KNN_HIT.itemsize)
+                _check(lib().bvh_radius_search(ctx.handle, C.byref(self.result), p_inp, _ptr(points), n, flags, offsets.ptr, hits.ptr, cap, C.byref(total)), what)
+                if total.value <= cap:
+                    break
+                hits.free(); hits = None
+                cap = total.value
+            return offsets.download(np.uint32, n + 1), hits.download(KNN_HIT, total.value)
         finally:
             offsets.free()
             if hits is not None:

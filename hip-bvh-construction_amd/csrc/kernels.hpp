@@ -214,6 +214,18 @@ void launch_hits_fill(hipStream_t s, int layout, int tri_format, int sorted, con
                       uint32_t n_vertices, const void* d_rays, uint32_t n_rays, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root,
                       uint32_t* d_offsets, void* d_hits, uint64_t capacity, const uint64_t* d_total, uint32_t* d_overflow, const uint32_t* d_parent);
 
+// ---- radius searches (radius.hip): bvh_radius_search's kernels, tree / triangle / point arguments as launch_closest_point's.  launch_radius_count:
+// k_radius_count (short stack; d_offsets[i] = query i's number of accepted candidates) + k_radius_deep (stackless, returns at once while *d_overflow == 0) +
+// launch_overlap_scan.  launch_radius_fill: k_radius_fill + k_radius_deep, which return at once unless *d_total <= capacity and *d_total < 2^32; query i's
+// bvh_knn_hit records go to d_hits[d_offsets[i] ..], in ascending (dist2, prim) order when sorted != 0.  Each pass has an overflow word of its own, zeroed
+// before the launches
+void launch_radius_count(hipStream_t s, int layout, int tri_format, const void* d_tris, const void* d_vertices, const void* d_indices, uint32_t n_vertices,
+                         const void* d_points, uint32_t n_points, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root, uint32_t* d_offsets,
+                         uint32_t* d_overflow, const uint32_t* d_parent, uint64_t* d_sums, uint64_t* d_total);
+void launch_radius_fill(hipStream_t s, int layout, int tri_format, int sorted, const void* d_tris, const void* d_vertices, const void* d_indices,
+                        uint32_t n_vertices, const void* d_points, uint32_t n_points, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root,
+                        uint32_t* d_offsets, void* d_hits, uint64_t capacity, const uint64_t* d_total, uint32_t* d_overflow, const uint32_t* d_parent);
+
 // ---- instanced scenes (scene.hip): bvh_scene's kernels.  SceneBlas: the device copy of one validated bvh_blas (64 bytes, read whole when a ray enters an
 // instance); tris = Triangle[n] / float[9n] / the vertices of INDEXED input, idx = INDEXED indices, parent = the BLAS's k_refit_plan plan (u32[2n-1]).
 struct SceneBlas { const void* nodes; const void* leaves; const void* tris; const void* idx; const uint32_t* parent; uint32_t n, root, layout, fmt, nv, pad; };
@@ -260,6 +272,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius();
 
 } // namespace bvh

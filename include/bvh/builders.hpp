@@ -219,6 +219,16 @@ public:
         check(bvh_knn(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, d_points, n, k, d_hits, d_counts), "knn");
     }
 
+    // beyond the reference (bvh_radius_search): every triangle within each query's radius, as offsets + (dist2, prim) records (ascending per query with
+    // BVH_RADIUS_SORTED in flags); against the same tree and triangles as intersect.  d_hits NULL: count only.  total given: the call waits for the total and
+    // stores it; nullptr: asynchronous, the fill decides on the device whether the capacity suffices
+    void radiusSearch(Context& context, const bvh_point_query* d_points, u32 n, u32 flags, u32* d_offsets, bvh_knn_hit* d_hits, u64 capacity, u64* total = nullptr) {
+        uint64_t t = 0;
+        check(bvh_radius_search(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, d_points, n, flags, d_offsets, d_hits, capacity,
+                                total ? &t : nullptr), "radiusSearch");
+        if (total) *total = t;
+    }
+
     // beyond the reference (bvh_overlap): which primitives' boxes each query box touches, as offsets + primitive indices; BVH_OVERLAP_SELF with the tree's own
     // primitive boxes gives every overlapping pair once.  d_prims NULL: count only.  Returns the total (the call waits for it)
     u64 overlap(Context& context, const bvh_aabb* d_boxes, u32 n, bvh_overlap_mode mode, u32* d_offsets, u32* d_prims, u64 capacity) {

@@ -4,7 +4,7 @@
  *   Ray       32 B, alignas(32) (src/Common.h:533-539; the record bvh_generate_rays writes)      bvh_hit 16 B (bvh_intersect's output, no counterpart)
  *   bvh_instance 64 B (one placed bottom-level tree of a bvh_scene)      bvh_instance_hit 32 B (bvh_scene_intersect's output); neither has a counterpart
  *   bvh_point_query 16 B (bvh_closest_point's input)      bvh_point_hit 32 B (its output); neither has a counterpart
- *   bvh_knn_hit 8 B (one entry of bvh_knn's lists, which reads bvh_point_query too); no counterpart
+ *   bvh_knn_hit 8 B (one entry of bvh_knn's lists and one record of bvh_radius_search's slices; both read bvh_point_query too); no counterpart
  * Usable from C, C++ and HIP device code. */
 #ifndef BVH_TYPES_H
 #define BVH_TYPES_H
@@ -31,7 +31,8 @@ typedef struct { float t, u, v; uint32_t prim_idx; } bvh_hit;
  * (u, v) = the weights of v2 and v3 */
 typedef struct { bvh_float3 point; float radius; } bvh_point_query;
 typedef struct { bvh_float3 point; float dist2; float u, v; uint32_t prim_idx, reserved; } bvh_point_hit;
-/* one entry of a k-nearest list: the squared distance of triangle prim_idx's closest point (an unused slot: {radius*radius, BVH_INVALID}) */
+/* one entry of a k-nearest list (bvh_knn) or of a radius search's slice (bvh_radius_search): the squared distance of triangle prim_idx's closest point (an
+ * unused slot of a k-nearest list: {radius*radius, BVH_INVALID}; a slice has no unused slots) */
 typedef struct { float dist2; uint32_t prim_idx; } bvh_knn_hit;
 /* object_to_world: row-major 3x4 matrix {m00 m01 m02 m03, m10 .. m13, m20 .. m23}; world = M * (object, 1).  blas: index into the scene's bottom-level table */
 typedef struct { float object_to_world[12]; uint32_t blas; uint32_t reserved[3]; } bvh_instance;

@@ -336,6 +336,54 @@ int  bvh_knn(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /
              const bvh_point_query* d_points, uint32_t n_points, uint32_t k, bvh_knn_hit* d_hits /* [n_points * k], query i's list at d_hits[i*k .. i*k+k) */,
              uint32_t* d_counts /* [n_points] or NULL */);
 
+/* ---- radius searches (no counterpart in the reference) ---------------------------------------------------------------------------------
+ * Which triangles lie within the radius of each query point, ALL of them?  The fixed-radius range search: SPH and particle neighbourhoods on point clouds,
+ * contact and proximity detection with a margin, narrow-band distance fields where more than the nearest triangle matters, brush spheres of mesh painting and
+ * selection, density estimates.  One call instead of bvh_knn with a k that may be too small (its lists are capped at BVH_KNN_MAX_K), or bvh_overlap with the
+ * sphere's box and an exact-distance filter on the host.
+ * tree / tris: exactly as bvh_closest_point — any bvh_result in either layout, read as it is (a build's, a refit's, an optimised or a caller-filled one on the
+ * ctx's device), triangles in any bvh_tri_format validated as by bvh_build_ex (NULL: tree->d_tris is read as Triangle[n_leaves]); nothing in the tree is
+ * written; a primitive or child index out of range is never followed, and arrays that are not a tree end in finite time with unspecified answers.
+ * Candidate and acceptance are bvh_closest_point's, word for word: the candidate of a triangle is Ericson's ClosestPtPointTriangle in f32, operation for
+ * operation as stated there, dist2 = (dx*dx + dy*dy) + dz*dz; it is accepted iff dist2 <= r2, r2 = radius*radius in f32.  An infinite radius accepts every
+ * triangle whose dist2 is not NaN (a triangle with a NaN vertex is never accepted).  Queries with a NaN coordinate, a NaN radius or radius < 0 are dead: they
+ * accept nothing.  radius 0 (or -0) accepts the triangles at dist2 == 0.
+ * Answer: query i's set is ALL its accepted candidates, as {dist2, prim_idx} records (bvh_knn_hit) in compressed-row form: d_hits[d_offsets[i] ..
+ * d_offsets[i+1]) is query i's slice, d_offsets[0] = 0, d_offsets[n_points] = the total.  Each primitive appears at most once per slice.  There is no padding
+ * and there are no miss records: an empty slice is "nothing within r".  With d_hits == NULL the call only counts: d_offsets is then the queries' neighbour
+ * counts in scanned form.
+ * Point clouds are served by degenerate triangles v1 == v2 == v3, as for bvh_knn: dist2 = |p - v1|^2 as (dx*dx + dy*dy) + dz*dz, prim_idx the point's index.
+ * Order inside a slice: without BVH_RADIUS_SORTED unspecified, but the same call on the same arrays gives the same bytes.  With BVH_RADIUS_SORTED each slice is
+ * in ascending (dist2, prim_idx) order, compared lexicographically; the whole d_hits array then does not depend on the builder, the layout, the scheduler, the
+ * triangle format or the traversal order, and the first min(k, count) records of a slice are bvh_knn's list.  Any other flag bit is an error.  The sorted fill
+ * inserts each record into its slice as it is found, which is quadratic in the slice's length: very long sorted slices (thousands of neighbours per query)
+ * are the caller's to avoid, or to fill unsorted and sort themselves.
+ * Box tests are bvh_closest_point's conservative test (every box grows on every axis by 2^-16 times its largest |coordinate|, its f32 squared
+ * distance to the point is lb, the subtree is kept iff lb * (1 - 2^-20) <= the bound) against r2 for the whole walk: the bound never shrinks.  A query is
+ * well-conditioned when every accepted triangle satisfies §8e's condition: the f64 squared distance from the point to that triangle's box, grown by 2^-17
+ * times its largest |coordinate|, is <= its dist2.  On such queries no ancestor of an accepted triangle is culled and the set is exact.  On
+ * EVERY query each reported record is an accepted candidate of its primitive with a bit-equal dist2, and the slice is a subset of the true set.
+ * Passes: the call always counts, then scans the counts into d_offsets, and keeps the 64-bit total in a device word.  It fills d_hits iff d_hits != NULL,
+ * total <= capacity and total < 2^32; that decision is made ON THE DEVICE (the fill launch reads the total word and returns at once), so the call stays
+ * asynchronous on the ctx's stream.  If the fill is skipped d_hits is not touched and d_offsets is still complete.  With total_out != NULL the call blocks on
+ * an 8-byte read-back into pinned words and stores the total; a host that guessed too small a capacity re-allocates and calls again.  A total of 2^32 or more
+ * saturates d_offsets at 0xFFFFFFFF; if total_out was given the call then returns BVH_E_TOO_LARGE (with *total_out set).  d_hits is never written outside
+ * query i's slice, nor past the total.
+ * There is no depth limit: a query whose short stack would overflow, or whose walk exceeds the node count, is redone by a stackless pass through bvh_refit's
+ * parent plan, cached for the ctx's own tree as for bvh_intersect and made per call for caller-owned arrays.  Count and fill agree on every query's set
+ * whichever pass served it.
+ * Errors (nothing is written or enqueued, BVH_E_INVALID_ARG): bvh_closest_point's (NULL ctx / tree / d_points, n_leaves < 2, layout not 0 or 1, NULL d_nodes,
+ * layout 1 with NULL d_leaves, root not an internal node, no triangles or a tris format error, n_leaves larger than the ctx's capacity: call bvh_ctx_reserve
+ * first); NULL d_offsets; a flag bit other than BVH_RADIUS_SORTED; n_points >= 2^30; d_offsets or d_hits (capacity records) overlapping d_points or each other.
+ * n_points == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.
+ * bvh_ctx_kernel_times reports k_radius_count, k_radius_deep (after each pass), k_overlap_scan (the scan is bvh_overlap's), k_radius_fill and, when the plan is
+ * made, k_refit_plan. */
+#define BVH_RADIUS_SORTED 1u
+int  bvh_radius_search(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
+                       const bvh_point_query* d_points, uint32_t n_points, uint32_t flags /* 0 or BVH_RADIUS_SORTED */,
+                       uint32_t* d_offsets /* u32[n_points + 1], device */, bvh_knn_hit* d_hits /* [capacity], device, or NULL: count only */,
+                       uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+
 /* ---- box queries (no counterpart in the reference) -------------------------------------------------------------------------------------
  * Which primitives does each box touch?  The broad phase of collision detection, region selection, culling against an axis-aligned volume, neighbour gathering
  * on a bvh_build_boxes tree, "which instances does this volume touch" on a scene's top-level tree.
