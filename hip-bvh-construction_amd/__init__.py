@@ -77,6 +77,7 @@ EXPORTS = [
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
+    "bvh_split_refs", "bvh_remap_leaves",
 ]
 
 
@@ -116,6 +117,7 @@ _QUERY_IDS = {"closest": QUERY_CLOSEST, "any": QUERY_ANY}
 OVERLAP_BOXES, OVERLAP_SELF = 0, 1   # bvh_overlap_mode
 HITS_SORTED = 1                      # BVH_HITS_SORTED (bvh_intersect_all's flag)
 RADIUS_SORTED = 1                    # BVH_RADIUS_SORTED (bvh_radius_search's flag)
+SPLIT_MAX_DEPTH = 16                 # BVH_SPLIT_MAX_DEPTH (bvh_split_refs)
 ABI_VERSION = 4                      # BVH_ABI_VERSION of include/bvh_mi355x.h this binding was written against
 # bvh_option (bvh_ctx_set_option) and the names this harness accepts for the values
 OPT_HPLOC_SCHEDULER, OPT_LBVH_SCHEDULER, OPT_SORT_TEST_KNOBS, OPT_PLOC_SCHEDULER = 0, 1, 2, 3
@@ -213,6 +215,8 @@ def lib() -> C.CDLL:
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_intersect_all": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_radius_search": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_split_refs": ([vp, C.POINTER(BuildInput), u32, C.c_float, u32, vp, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_remap_leaves": ([vp, C.POINTER(Result), vp, u32], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -357,6 +361,49 @@ class Context:
     def alloc(self, nbytes: int) -> DeviceBuffer:
         return DeviceBuffer(self, nbytes)
 
+    def split_refs(self, tris=None, sa_max: float = 3.4028234663852886e38, max_depth: int = SPLIT_MAX_DEPTH, n: int | None = None, vertices=None, indices=None,
+                   n_vertices: int = 0, tri_format: int = TRI_PADDED64, count_only: bool = False, keep_on_device: bool = False):
+        """bvh_split_refs: early split clipping.  ``tris`` a host TRIANGLE array (uploaded for the call) or device inputs in ``tri_format`` as for build_ex
+        (with ``n``).  Count, allocate, fill.  Returns (offsets u32[n + 1], ref_boxes AABB[total], ref_prims u32[total], total) as host arrays —
+        triangle p's references are [offsets[p], offsets[p + 1]) — or, with ``keep_on_device``, the three DeviceBuffers (the caller frees them) and the total.
+        ``count_only``: (offsets, None, None, total)."""
+        own = None
+        if isinstance(tris, np.ndarray):
+            if tris.dtype != TRIANGLE:
+                raise BvhError("tris must have dtype TRIANGLE (64-byte records)")
+            n = tris.shape[0]
+            own = tris = self.upload(np.ascontiguousarray(tris))
+            tri_format = TRI_PADDED64
+        elif n is None:
+            raise BvhError("n is required for device inputs")
+        inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                         _ptr(indices) if indices is not None else None, n_vertices, 0)
+        offsets = self.alloc((n + 1) * 4)
+        boxes = prims = None
+        done = False
+        try:
+            total = C.c_uint64()
+            _check(lib().bvh_split_refs(self.handle, C.byref(inp), n, float(sa_max), int(max_depth), offsets.ptr, None, None, 0, C.byref(total)), "bvh_split_refs")
+            if count_only:
+                return offsets.download(np.uint32, n + 1), None, None, int(total.value)
+            cap = int(total.value)
+            boxes = self.alloc(max(cap, 1) * AABB.itemsize); prims = self.alloc(max(cap, 1) * 4)
+            _check(lib().bvh_split_refs(self.handle, C.byref(inp), n, float(sa_max), int(max_depth), offsets.ptr, boxes.ptr, prims.ptr, cap, C.byref(total)),
+                   "bvh_split_refs")
+            if total.value != cap:
+                raise BvhError(f"bvh_split_refs: the fill found {total.value} references, the count pass {cap}")
+            if keep_on_device:
+                done = True
+                return offsets, boxes, prims, cap
+            return offsets.download(np.uint32, n + 1), boxes.download(AABB, cap), prims.download(np.uint32, cap), cap
+        finally:
+            if own is not None:
+                own.free()                                # (hipFree waits for the kernels that read it)
+            if not done:
+                for bfr in (offsets, boxes, prims):
+                    if bfr is not None:
+                        bfr.free()
+
     def close(self) -> None:
         if self.handle:
             for sc in list(self._scenes):
@@ -385,6 +432,7 @@ class _Builder:
         self.m_cost = 0.0
         self.m_timer = {}
         self._ctx = None
+        self._split = None                                # build_split's device arrays: {"tris", "offsets", "ref_boxes", "ref_prims", "n_tris", "total"}
 
     def build(self, context: Context, primitives, on_device: bool = False, n: int | None = None) -> "_Builder":
         """``primitives``: numpy array of dtype TRIANGLE (host; copied H2D untimed like the reference) or, with
@@ -398,6 +446,7 @@ class _Builder:
         elif n is None:
             raise BvhError("n is required for device inputs")
         self._ctx = context
+        self._free_split()                                # (a tree over triangles: no kept references)
         _check(lib().bvh_build(context.handle, self.ALGO, _ptr(primitives), n, int(on_device), C.byref(self.result), C.byref(self.timings)),
                f"{ALGO_NAMES[self.ALGO]}::build")
         return self._publish()
@@ -406,12 +455,13 @@ class _Builder:
                  morton_bits: int = 30) -> "_Builder":
         """bvh_build_ex: device inputs in any bvh_tri_format, 30- or 60-bit Morton codes."""
         self._ctx = context
+        self._free_split()
         inp = BuildInput(tri_format, morton_bits, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
                          _ptr(indices) if indices is not None else None, n_vertices, 0)
         _check(lib().bvh_build_ex(context.handle, self.ALGO, C.byref(inp), n, C.byref(self.result), C.byref(self.timings)), f"{ALGO_NAMES[self.ALGO]}::build_ex")
         return self._publish()
 
-    def build_boxes(self, context: Context, boxes, n: int | None = None, morton_bits: int = 30) -> "_Builder":
+    def build_boxes(self, context: Context, boxes, n: int | None = None, morton_bits: int = 30, _keep_split: bool = False) -> "_Builder":
         """bvh_build_boxes: a tree over caller-supplied boxes — a host AABB array (copied to the device for the call) or a device buffer / int address with
         ``n``.  The result has no triangles (d_tris NULL): intersect / refit need explicit ones."""
         own = None
@@ -423,6 +473,8 @@ class _Builder:
         elif n is None:
             raise BvhError("n is required for device boxes")
         self._ctx = context
+        if not _keep_split:
+            self._free_split()                            # (build_split's arrays belong to the tree it built)
         try:
             _check(lib().bvh_build_boxes(context.handle, self.ALGO, _ptr(boxes), n, int(morton_bits), C.byref(self.result), C.byref(self.timings)),
                    f"{ALGO_NAMES[self.ALGO]}::build_boxes")
@@ -430,6 +482,61 @@ class _Builder:
             if own is not None:
                 own.free()                                # (hipFree waits for the build that read it)
         return self._publish()
+
+    def build_split(self, context: Context, primitives, sa_max: float, max_depth: int = SPLIT_MAX_DEPTH, morton_bits: int = 30, relabel: bool = True) -> "_Builder":
+        """Early split clipping in front of the build: bvh_split_refs (count, allocate, fill), bvh_build_boxes over the reference boxes and, with ``relabel``,
+        bvh_remap_leaves so that the leaves name the original triangles.  ``primitives``: a host TRIANGLE array.  The builder keeps the triangles and the
+        reference arrays on the device (``split_arrays()`` downloads them); a later intersect / closest_point on this builder passes the triangles as ``tris``
+        by default.  A tree over fewer than 2 references cannot be built (bvh_build_boxes' rule).  Not for refit / refit_subset (include/bvh_mi355x.h)."""
+        if not isinstance(primitives, np.ndarray) or primitives.dtype != TRIANGLE:
+            raise BvhError("primitives must be a host array of dtype TRIANGLE (64-byte records)")
+        self._free_split()
+        n = primitives.shape[0]
+        d_tris = context.upload(np.ascontiguousarray(primitives))
+        try:
+            offsets, boxes, prims, total = context.split_refs(tris=d_tris, n=n, sa_max=sa_max, max_depth=max_depth, keep_on_device=True)
+        except Exception:
+            d_tris.free()
+            raise
+        self._split = {"tris": d_tris, "offsets": offsets, "ref_boxes": boxes, "ref_prims": prims, "n_tris": n, "total": total}
+        self.build_boxes(context, boxes, n=total, morton_bits=morton_bits, _keep_split=True)
+        if relabel:
+            self.remap_leaves(prims, n_map=total)
+        return self
+
+    def remap_leaves(self, map, n_map: int | None = None) -> "_Builder":
+        """bvh_remap_leaves: every leaf's primitive index q < n_map becomes map[q].  ``map``: a numpy array (converted to u32 and uploaded for the call) or a
+        device buffer of u32 (DeviceBuffer / int address, with ``n_map``)."""
+        if self._ctx is None:
+            raise BvhError("remap_leaves needs a built tree")
+        own = None
+        if isinstance(map, np.ndarray):
+            host = np.ascontiguousarray(map, dtype=np.uint32).ravel()
+            n_map = host.shape[0]
+            own = map = self._ctx.upload(host)
+        elif n_map is None:
+            n_map = map.nbytes // 4 if isinstance(map, DeviceBuffer) else None
+            if n_map is None:
+                raise BvhError("n_map is required for device maps")
+        try:
+            _check(lib().bvh_remap_leaves(self._ctx.handle, C.byref(self.result), _ptr(map) or None, int(n_map)), f"{ALGO_NAMES[self.ALGO]}::remap_leaves")
+        finally:
+            if own is not None:
+                own.free()                                # (hipFree waits for the kernel that read it)
+        return self
+
+    def split_arrays(self):
+        """build_split's (offsets u32[n_tris + 1], ref_boxes AABB[total], ref_prims u32[total]) as host arrays"""
+        sp = self._split
+        if sp is None:
+            raise BvhError("split_arrays needs build_split")
+        return (sp["offsets"].download(np.uint32, sp["n_tris"] + 1), sp["ref_boxes"].download(AABB, sp["total"]), sp["ref_prims"].download(np.uint32, sp["total"]))
+
+    def _free_split(self) -> None:
+        if self._split is not None:
+            for k in ("tris", "offsets", "ref_boxes", "ref_prims"):
+                self._split[k].free()
+            self._split = None
 
     def refit(self, primitives, on_device: bool = False, n: int | None = None) -> "_Builder":
         """bvh_refit: recompute every box of this builder's tree from new triangle positions (same count, same order), topology kept.
@@ -520,6 +627,8 @@ class _Builder:
             if n_rays is None:
                 raise BvhError("n_rays is required for device rays")
         inp = None
+        if tris is None and vertices is None and indices is None and self._split is not None:
+            tris, tri_format = self._split["tris"], TRI_PADDED64      # (a build_split tree has no d_tris of its own)
         if tris is not None or vertices is not None or indices is not None:
             inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
                              _ptr(indices) if indices is not None else None, n_vertices, 0)
@@ -560,6 +669,8 @@ class _Builder:
             if n_points is None:
                 raise BvhError("n_points is required for device points")
         inp = None
+        if tris is None and vertices is None and indices is None and self._split is not None:
+            tris, tri_format = self._split["tris"], TRI_PADDED64      # (a build_split tree has no d_tris of its own)
         if tris is not None or vertices is not None or indices is not None:
             inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
                              _ptr(indices) if indices is not None else None, n_vertices, 0)

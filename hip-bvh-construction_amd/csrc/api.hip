@@ -96,6 +96,10 @@ struct bvh_ctx {
     bool subset_dirty = false;
     uint64_t map_serial = 0;
     uint32_t map_n = 0, map_root = 0;
+    // bvh_split_refs' words, outside the arena (the call needs no tree and must not move one): u64 total | u32 heavy count | (pad to 64 bytes) |
+    // u64 scan sums[OVERLAP_SCAN_BLOCKS] | u32 heavy list[split_cap].  Calls on the ctx's stream are ordered, so one set serves them all
+    char* split_words = nullptr;
+    uint32_t split_cap = 0;
 };
 
 // bvh_scene: device memory of its own (one allocation, carved as below), outside the ctx's arena; only the top-level build uses the arena
@@ -397,7 +401,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); }); }
     *out = c;
     return 0;
 }
@@ -410,6 +414,7 @@ void bvh_ctx_destroy(bvh_ctx* c) {
     if (c->arena) hipFree(c->arena);
     if (c->tris) hipFree(c->tris);
     if (c->subset_words) hipFree(c->subset_words);
+    if (c->split_words) hipFree(c->split_words);
     for (auto& e : c->ev) if (e) hipEventDestroy(e);
     if (c->h_pinned) hipHostFree(c->h_pinned);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -1115,6 +1120,100 @@ int bvh_radius_search(bvh_ctx* c, const bvh_result* tree, const bvh_build_input*
         *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
         if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
     }
+    return 0;
+}
+
+// ---- early split clipping (Utility::doEarlySplitClipping, src/Utility.cpp:456-538, as a device pass) ----------------------------------------------
+// bvh_split_refs' words, sized by the largest n seen.  The new block is allocated before the old one is released: a failed allocation changes nothing
+static constexpr size_t SPLIT_HEAD_BYTES = 64 + (size_t)OVERLAP_SCAN_BLOCKS * sizeof(u64);
+static int ensure_split_words(bvh_ctx* c, uint32_t n) {
+    if (c->split_words && n <= c->split_cap) return 0;
+    char* p = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), SPLIT_HEAD_BYTES + (size_t)n * sizeof(u32)));
+    if (c->split_words) {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipFree(c->split_words);
+        if (e != hipSuccess) { (void)hipFree(p); return -(int)e; }
+    }
+    c->split_words = p; c->split_cap = n;
+    return 0;
+}
+
+// count -> scan -> fill on one stream, as bvh_intersect_all; every argument is checked before anything is enqueued, so an error writes nothing.  Whether the fill
+// runs is decided on the device (split.hip); the host only waits when the caller asks for the total.  The arena is not touched: the call needs no tree
+int bvh_split_refs(bvh_ctx* c, const bvh_build_input* in, uint32_t n, float sa_max, uint32_t max_depth, uint32_t* d_offsets, bvh_aabb* d_ref_boxes,
+                   uint32_t* d_ref_prims, uint64_t capacity, uint64_t* total_out) {
+    if (!c || !in || !d_offsets) return BVH_E_INVALID_ARG;
+    if (stage_extents_valid(in)) return BVH_E_INVALID_ARG;
+    if (n == 0 || n >= (1u << 30)) return BVH_E_INVALID_ARG;
+    if (!(sa_max >= 0.0f)) return BVH_E_INVALID_ARG;          // (NaN or negative)
+    if (max_depth > (uint32_t)BVH_SPLIT_MAX_DEPTH) return BVH_E_INVALID_ARG;
+    if ((d_ref_boxes == nullptr) != (d_ref_prims == nullptr)) return BVH_E_INVALID_ARG;
+    {   // the output ranges may not overlap each other, d_offsets or the input (the outputs are never written past 2^32 - 1 records: a larger total skips the fill)
+        struct Range { uintptr_t lo, hi; };
+        const uint64_t recs = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;
+        const Range ro{ (uintptr_t)d_offsets, (uintptr_t)d_offsets + ((uint64_t)n + 1u) * sizeof(u32) };
+        const Range rb{ (uintptr_t)d_ref_boxes, (uintptr_t)d_ref_boxes + (d_ref_boxes ? recs * sizeof(bvh_aabb) : 0u) };
+        const Range rp{ (uintptr_t)d_ref_prims, (uintptr_t)d_ref_prims + (d_ref_prims ? recs * sizeof(u32) : 0u) };
+        Range i0{ 0, 0 }, i1{ 0, 0 };
+        switch (in->tri_format) {
+            case BVH_TRI_PADDED64: i0 = { (uintptr_t)in->d_tris, (uintptr_t)in->d_tris + (uint64_t)n * 64u }; break;
+            case BVH_TRI_PACKED36: i0 = { (uintptr_t)in->d_tris, (uintptr_t)in->d_tris + (uint64_t)n * 36u }; break;
+            default: i0 = { (uintptr_t)in->d_vertices, (uintptr_t)in->d_vertices + (uint64_t)in->n_vertices * 12u };
+                     i1 = { (uintptr_t)in->d_indices, (uintptr_t)in->d_indices + (uint64_t)n * 12u }; break;
+        }
+        auto cross = [](const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; };
+        if (cross(ro, rb) || cross(ro, rp) || cross(rb, rp) || cross(ro, i0) || cross(ro, i1) || cross(rb, i0) || cross(rb, i1) || cross(rp, i0) || cross(rp, i1))
+            return BVH_E_INVALID_ARG;
+    }
+    Bind b(c->device);
+    int r = ensure_split_words(c, n); if (r) return r;
+    hipStream_t s = c->stream;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    u64* const total = reinterpret_cast<u64*>(c->split_words);
+    u32* const heavy_count = reinterpret_cast<u32*>(c->split_words + 8);
+    u64* const sums = reinterpret_cast<u64*>(c->split_words + 64);
+    u32* const heavy_list = reinterpret_cast<u32*>(c->split_words + SPLIT_HEAD_BYTES);
+    hipError_t e = hipMemsetAsync(c->split_words, 0, 16, s);
+    if (e == hipSuccess) {
+        launch_split_count(s, (int)in->tri_format, in->d_tris, in->d_vertices, in->d_indices, in->n_vertices, n, sa_max, max_depth, d_offsets, heavy_list, heavy_count,
+                           sums, total);
+        if (d_ref_boxes)
+            launch_split_fill(s, (int)in->tri_format, in->d_tris, in->d_vertices, in->d_indices, in->n_vertices, n, sa_max, max_depth, d_offsets, d_ref_boxes,
+                              d_ref_prims, capacity, total, heavy_list, heavy_count);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return herr(e);
+    if (install.on) c->recorder.mark(s, nullptr);
+    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
+        u32* const rb = c->h_pinned + 8;
+        r = read_back(c, reinterpret_cast<const u32*>(total), 2, nullptr, 0, rb); if (r) return r;
+        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
+        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
+    }
+    return 0;
+}
+
+// every leaf's primitive index through a map.  Topology and boxes stay: the ctx's cached parent plan remains valid (tree_serial is not bumped); the cached leaf
+// map of bvh_refit_subset describes the old indices and is dropped
+int bvh_remap_leaves(bvh_ctx* c, bvh_result* io, const uint32_t* d_map, uint32_t n_map) {
+    int r = refit_check(c, io); if (r) return r;
+    if (!d_map) return BVH_E_INVALID_ARG;
+    const uint32_t n = io->n_leaves;
+    {   // the map may not overlap the leaf records
+        const char* w = io->layout == 0 ? (const char*)io->d_nodes + (uint64_t)(n - 1) * sizeof(bvh2_node) : (const char*)io->d_leaves;
+        const uint64_t w_bytes = (uint64_t)n * (io->layout == 0 ? sizeof(bvh2_node) : sizeof(bvh_primref)), m_bytes = (uint64_t)n_map * sizeof(u32);
+        const uintptr_t w0 = (uintptr_t)w, m0 = (uintptr_t)d_map;
+        if (n_map && m0 < w0 + w_bytes && w0 < m0 + m_bytes) return BVH_E_INVALID_ARG;
+    }
+    Bind b(c->device);
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    c->map_serial = 0;
+    launch_remap_leaves(c->stream, io->d_nodes, io->d_leaves, (int)io->layout, n, d_map, n_map);
+    HIP_TRY(hipGetLastError());
+    if (install.on) c->recorder.mark(c->stream, nullptr);
     return 0;
 }
 

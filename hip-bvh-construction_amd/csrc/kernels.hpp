@@ -226,6 +226,19 @@ void launch_radius_fill(hipStream_t s, int layout, int tri_format, int sorted, c
                         uint32_t n_vertices, const void* d_points, uint32_t n_points, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root,
                         uint32_t* d_offsets, void* d_hits, uint64_t capacity, const uint64_t* d_total, uint32_t* d_overflow, const uint32_t* d_parent);
 
+// ---- early split clipping (split.hip): bvh_split_refs' kernels, triangle arguments as launch_intersect's.  launch_split_count: k_split_count (d_offsets[p] =
+// triangle p's number of references; triangles a wave will fill are appended to d_heavy_list, u32[n], counted in *d_heavy_count, zeroed before the launch) +
+// launch_overlap_scan.  launch_split_fill: k_split_fill (one triangle per lane) + k_split_heavy (one listed triangle per wave), which return at once unless
+// *d_total <= capacity and *d_total < 2^32; triangle p's references go to d_ref_boxes / d_ref_prims [d_offsets[p] ..].  launch_remap_leaves: bvh_remap_leaves' kernel
+constexpr uint32_t SPLIT_HEAVY_BLOCKS = 1024;
+void launch_split_count(hipStream_t s, int tri_format, const void* d_tris, const void* d_vertices, const void* d_indices, uint32_t n_vertices, uint32_t n,
+                        float sa_max, uint32_t max_depth, uint32_t* d_offsets, uint32_t* d_heavy_list, uint32_t* d_heavy_count, uint64_t* d_sums,
+                        uint64_t* d_total);
+void launch_split_fill(hipStream_t s, int tri_format, const void* d_tris, const void* d_vertices, const void* d_indices, uint32_t n_vertices, uint32_t n,
+                       float sa_max, uint32_t max_depth, const uint32_t* d_offsets, void* d_ref_boxes, uint32_t* d_ref_prims, uint64_t capacity,
+                       const uint64_t* d_total, const uint32_t* d_heavy_list, const uint32_t* d_heavy_count);
+void launch_remap_leaves(hipStream_t s, void* d_nodes, void* d_leaves, int layout, uint32_t n, const uint32_t* d_map, uint32_t n_map);
+
 // ---- instanced scenes (scene.hip): bvh_scene's kernels.  SceneBlas: the device copy of one validated bvh_blas (64 bytes, read whole when a ray enters an
 // instance); tris = Triangle[n] / float[9n] / the vertices of INDEXED input, idx = INDEXED indices, parent = the BLAS's k_refit_plan plan (u32[2n-1]).
 struct SceneBlas { const void* nodes; const void* leaves; const void* tris; const void* idx; const uint32_t* parent; uint32_t n, root, layout, fmt, nv, pad; };
@@ -272,6 +285,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split();
 
 } // namespace bvh

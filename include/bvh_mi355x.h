@@ -420,6 +420,61 @@ int  bvh_overlap(bvh_ctx* ctx, const bvh_result* tree, const bvh_aabb* d_boxes, 
                  uint32_t* d_offsets /* u32[n_boxes + 1], device */, uint32_t* d_prims /* u32[capacity], device, or NULL: count only */,
                  uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
 
+/* ---- early split clipping (Utility::doEarlySplitClipping, src/Utility.cpp:456-538: the PrimRef[] front end of the reference's LBVH builders) -------------
+ * Large triangles become several REFERENCES {box, triangle index}: a box whose surface area exceeds sa_max is halved at its centre on its longest axis until
+ * every piece is small enough, and the tree is then built over the pieces (bvh_build_boxes), so a wall that spans the scene no longer owns a scene-sized leaf.
+ * Several leaves refer to one triangle.  The reference does this on the host, one queue item at a time; here it is a count -> scan -> fill device pass.
+ * Input: any bvh_tri_format (in->morton_bits is not read), n triangles, device pointers.
+ * Root box: triangle p's root box is exactly the box stage E writes for it (bvh_stage_extents_ex; the same device function), NaN / infinity clamping included;
+ * for finite triangles that is the reference's Aabb::grow of the three vertices.
+ * refs(box, depth) — f32 throughout, operation for operation, no contraction; ext = max - min:
+ *   area = 2 * (ext.x * ext.y + ext.x * ext.z + ext.y * ext.z)                     (Aabb::area, src/Common.h:361-365, same association)
+ *   dim  = 0 if ext.x > ext.y && ext.x > ext.z, else 1 if ext.y > ext.z, else 2    (Aabb::maximumExtentDim, :351-359)
+ *   c    = (max[dim] + min[dim]) * 0.5f                                            (Aabb::center, :347)
+ *   EMIT the box as one reference if !(area > sa_max) (a NaN area emits at once), or depth == max_depth, or !(min[dim] < c && c < max[dim]) (the cut would make
+ *   no progress); OTHERWISE L = the box with max[dim] = c, R = the box with min[dim] = c, and the result is refs(L, depth + 1) followed by refs(R, depth + 1).
+ *   The last two emit rules are this library's: the reference has neither and does not terminate where they would fire.  Where neither fires the set of
+ *   references equals the reference's (tests/golden/split_*.primref), which it produces in breadth-first order.
+ * Output order (canonical): triangles in index order, and within a triangle the depth-first, left-first order above.  d_ref_boxes[d_offsets[p] ..
+ * d_offsets[p+1]) are triangle p's references and d_ref_prims holds p there; d_offsets[0] = 0, d_offsets[n] = the total.  The bytes depend neither on the
+ * triangle format nor on which internal path served a triangle (one lane per triangle, or one wave for a triangle with more than 64 references), and are the same
+ * on every call.  A triangle has at most 2^max_depth references.
+ * Passes: the call always counts, scans the counts into d_offsets and keeps the 64-bit total in a device word.  It fills iff both output pointers are non-NULL,
+ * total <= capacity and total < 2^32; that decision is made ON THE DEVICE, so the call stays asynchronous on the ctx's stream.  If the fill is skipped the output
+ * arrays are not touched and d_offsets is still complete.  With total_out != NULL the call blocks on an 8-byte read-back and stores the total; a total of 2^32 or
+ * more saturates d_offsets at 0xFFFFFFFF and the call then returns BVH_E_TOO_LARGE (with *total_out set).
+ * Identity: max_depth == 0 gives one reference per triangle — stage E's boxes and prims 0 .. n-1 — and so does sa_max = FLT_MAX for finite triangles (the
+ * reference's default saMax).  bvh_build_boxes over that output is byte-identical to bvh_build_ex on the triangles.
+ * Errors (nothing is written or enqueued, BVH_E_INVALID_ARG): NULL ctx / in / d_offsets, an input format error as in bvh_build_ex, n == 0 or n >= 2^30, sa_max
+ * NaN or < 0, max_depth > BVH_SPLIT_MAX_DEPTH, exactly one of d_ref_boxes / d_ref_prims NULL, output ranges (capacity records) that overlap each other,
+ * d_offsets or the input arrays.
+ * Memory: the ctx keeps 4 bytes per triangle plus 8 KiB outside the arena (the list of wave-filled triangles, the scan's sums, the total word), grown when n
+ * grows; the arena and every bvh_result in it are untouched.  bvh_ctx_kernel_times reports k_split_count, k_overlap_scan, k_split_fill and k_split_heavy.
+ *
+ * bvh_remap_leaves: every leaf's primitive index q becomes d_map[q] (layout 0: nodes[n-1+j].left; layout 1: d_leaves[j].prim_idx); a q >= n_map stays as it
+ * is; nothing else is written.  After bvh_build_boxes over d_ref_boxes, d_map = d_ref_prims makes the leaves name the ORIGINAL triangles.  Topology and boxes
+ * are untouched, so the ctx's cached parent plan stays valid; the cached leaf map of bvh_refit_subset is dropped.  Asynchronous on the ctx's stream.
+ * Errors (nothing written, BVH_E_INVALID_ARG): NULL ctx / io / d_map, a tree bvh_refit would reject, d_map (n_map words) overlapping the leaf records.
+ * Who accepts a relabelled tree (n_leaves references, primitive indices below the triangle count, several leaves per triangle) — always pass the ORIGINAL
+ * triangles explicitly as `tris` (the tree's own d_tris is NULL after bvh_build_boxes):
+ *   bvh_intersect, bvh_closest_point: answers as on the unsplit tree.  Records are ordered by (t, prim) / (dist2, prim) and a triangle reached through two leaves
+ *     gives the same record twice, so the answer does not change; a primitive index is only followed while it is < n_leaves, which every triangle index is.
+ *     Conservative culling carries over: a triangle's references tile its root box with closed halves.
+ *   bvh_scene_build: as a BLAS, with the original triangles as bvh_blas.tris.  bvh_download, bvh_checksum, bvh_to_lbvh_layout, bvh_trace (with the original
+ *     Triangle array), bvh_collapse4: read the arrays as any tree.
+ *   bvh_intersect_all, bvh_knn, bvh_radius_search, bvh_overlap: valid, but they report a triangle ONCE PER REFERENCE REACHED (duplicates within a slice; a
+ *     bvh_knn list can fill with one triangle's references).  BVH_OVERLAP_SELF compares reference positions before and triangle indices after a relabelling;
+ *     run it before.
+ *   bvh_sah_cost needs nothing but the tree and may run at any time; bvh_optimize likewise (it moves no leaf).  bvh_bvh4_cost indexes d_prim_aabbs by the
+ *     leaves' primitive index: run it BEFORE the relabelling, while d_prim_aabbs (the reference boxes) still matches the leaves.
+ *   bvh_refit, bvh_refit_ex, bvh_refit_subset: NOT applicable to a tree over references, relabelled or not — they would read Triangle[n_leaves] and give leaf j
+ *     the whole box of triangle j.  After the triangles move, split and build again. */
+#define BVH_SPLIT_MAX_DEPTH 16
+int  bvh_split_refs(bvh_ctx* ctx, const bvh_build_input* in, uint32_t n, float sa_max, uint32_t max_depth /* 0 .. BVH_SPLIT_MAX_DEPTH */,
+                    uint32_t* d_offsets /* u32[n + 1], device */, bvh_aabb* d_ref_boxes /* [capacity], device, or NULL: count only */,
+                    uint32_t* d_ref_prims /* u32[capacity], device, or NULL: count only */, uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+int  bvh_remap_leaves(bvh_ctx* ctx, bvh_result* io, const uint32_t* d_map /* u32[n_map], device */, uint32_t n_map);
+
 /* ---- tree optimisation (no counterpart in the reference) ---------------------------------------------------------------------------------
  * Lower a built tree's SAH by treelet restructuring (Karras & Aila, HPG 2013): bottom-up, every treelet of 7 entries whose root holds enough leaves is replaced
  * by its SAH-optimal topology over the same entries.  The fast LBVH builds come out close to HPLOC quality; PLOC++ / HPLOC trees gain a few percent.
