@@ -77,7 +77,7 @@ EXPORTS = [
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
-    "bvh_split_refs", "bvh_remap_leaves",
+    "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree",
 ]
 
 
@@ -129,6 +129,16 @@ class BuildInput(C.Structure):
     """bvh_build_input: device pointers; tri_format TRI_*, morton_bits 30 / 60"""
     _fields_ = [("tri_format", C.c_uint32), ("morton_bits", C.c_uint32), ("d_tris", C.c_void_p), ("d_vertices", C.c_void_p),
                 ("d_indices", C.c_void_p), ("n_vertices", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ManyOut(C.Structure):
+    """bvh_many_out: the six caller-owned output arrays of bvh_build_many"""
+    _fields_ = [("d_nodes", C.c_void_p), ("d_prim_aabbs", C.c_void_p), ("d_scene_extents", C.c_void_p), ("d_roots", C.c_void_p),
+                ("d_sorted_keys", C.c_void_p), ("d_sorted_vals", C.c_void_p)]
+
+
+MESH_RANGE = np.dtype([("first", "<u4"), ("count", "<u4")])                                                       # bvh_mesh_range
+MANY_LDS_MAX_PRIMS = 512             # BVH_MANY_LDS_MAX_PRIMS: larger meshes of a build_many batch go through the ordinary build
 
 
 class Blas(C.Structure):
@@ -217,6 +227,8 @@ def lib() -> C.CDLL:
         "bvh_radius_search": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_split_refs": ([vp, C.POINTER(BuildInput), u32, C.c_float, u32, vp, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_remap_leaves": ([vp, C.POINTER(Result), vp, u32], i32),
+        "bvh_build_many": ([vp, i32, C.POINTER(BuildInput), u32, vp, u32, C.POINTER(ManyOut), C.POINTER(Timings)], i32),
+        "bvh_many_tree": ([i32, C.POINTER(BuildInput), vp, u32, C.POINTER(ManyOut), u32, vp, C.POINTER(Result), C.POINTER(BuildInput)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -279,6 +291,150 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+def many_layout(counts):
+    """bvh_build_many's output layout: (out_off, node_off, total) for the meshes' triangle counts — mesh m's d_prim_aabbs / d_sorted_* slices start at
+    out_off[m] (the exclusive scan of the counts), its 2*count-1 node records at record node_off[m] = 2*out_off[m] - m; total = the sum of the counts."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    out_off = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64) if len(counts) else np.zeros(0, np.int64)
+    node_off = 2 * out_off - np.arange(len(counts), dtype=np.int64)
+    return out_off, node_off, int(counts.sum())
+
+
+def many_check_ranges(ranges, n_tris: int, tri_format: int = TRI_PADDED64) -> np.ndarray:
+    """the host-side part of bvh_build_many's validation: ``ranges`` (rows of (first, count), or a MESH_RANGE array) as a contiguous MESH_RANGE array; BvhError
+    for no mesh, a count < 2, first + count > n_tris, a PACKED36 first that is not a multiple of 4, or 2^30 triangles and more in all."""
+    if isinstance(ranges, np.ndarray) and ranges.dtype == MESH_RANGE:
+        first, count = ranges["first"].astype(np.int64), ranges["count"].astype(np.int64)
+    else:
+        r = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+        first, count = r[:, 0], r[:, 1]
+    if len(first) == 0:
+        raise BvhError("build_many needs at least one mesh")
+    if (first < 0).any() or (first >= 2 ** 32).any() or (count >= 2 ** 32).any():
+        raise BvhError("mesh ranges must fit 32 bits")
+    if (count < 2).any():
+        raise BvhError(f"mesh {int(np.argmax(count < 2))} has fewer than 2 triangles")
+    if (first + count > int(n_tris)).any():
+        raise BvhError(f"mesh {int(np.argmax(first + count > int(n_tris)))} reaches past the {int(n_tris)} triangles of the input")
+    if tri_format == TRI_PACKED36 and (first % 4 != 0).any():
+        raise BvhError(f"PACKED36: the first triangle of mesh {int(np.argmax(first % 4 != 0))} is not a multiple of 4 (its records would not be 16-byte aligned)")
+    if int(count.sum()) >= 2 ** 30:
+        raise BvhError("build_many: 2^30 triangles or more in one batch")
+    out = np.empty(len(first), dtype=MESH_RANGE)
+    out["first"], out["count"] = first, count
+    return out
+
+
+class ManyTrees:
+    """The trees of one Context.build_many call.  Owns the output buffers (and the input it uploaded); they live outside the context's arena, so later builds on
+    the context leave them alone and ``blas(m)`` can go straight into a Scene on the same context."""
+
+    def __init__(self, ctx, algo, inp, n_tris, ranges, out, buffers):
+        self.ctx, self.algo, self.input, self.n_tris, self.ranges, self.out = ctx, int(algo), inp, int(n_tris), ranges, out
+        self._buffers = buffers                           # DeviceBuffers kept alive: outputs, uploaded inputs
+        self.n_meshes = len(ranges)
+        self.out_off, self.node_off, self.total = many_layout(ranges["count"])
+        self.timings = Timings()
+        self._roots = None
+
+    def roots(self) -> np.ndarray:
+        """u32[n_meshes]: every mesh's root (read back once; two-pass: all 0, no read-back)"""
+        if self._roots is None:
+            if self.algo == ALGO_TWOPASS:
+                self._roots = np.zeros(self.n_meshes, dtype=np.uint32)
+            else:
+                self._roots = np.empty(self.n_meshes, dtype=np.uint32)
+                _check(lib().bvh_dev_download(self.ctx.handle, self._roots.ctypes.data, self.out.d_roots, self._roots.nbytes), "bvh_dev_download")
+        return self._roots
+
+    def _slice(self, m: int):
+        r, t = Result(), BuildInput()
+        roots = self.roots()
+        _check(lib().bvh_many_tree(self.algo, C.byref(self.input), self.ranges.ctypes.data, self.n_meshes, C.byref(self.out), int(m), roots.ctypes.data,
+                                   C.byref(r), C.byref(t)), "bvh_many_tree")
+        return r, t
+
+    def tree(self, m: int) -> Result:
+        """bvh_many_tree: mesh m's slice as a Result"""
+        return self._slice(m)[0]
+
+    def tris(self, m: int) -> BuildInput:
+        """the BuildInput that names mesh m's triangles"""
+        return self._slice(m)[1]
+
+    def blas(self, m: int) -> Blas:
+        """mesh m as a bottom-level tree for Scene.build (the scene's context must be this one's device; the call orders nothing: synchronize first if the scene
+        lives on another context)"""
+        r, t = self._slice(m)
+        return Blas(r, t)
+
+    def builder(self, m: int) -> "_Builder":
+        """mesh m's tree behind the builders' query / refit / download methods (intersect, closest_point, knn, refit_ex ...).  Trees from PACKED36 / INDEXED input
+        take their triangles as those methods' tris / vertices / indices arguments (``tris(m)`` names them); reserve the context for the mesh's size first."""
+        b = BUILDERS[self.algo]()
+        b.result, b._ctx, b._many = self.tree(m), self.ctx, self
+        return b._publish()
+
+    def download(self, m: int) -> dict:
+        """mesh m's arrays as numpy: dict(nodes, leaves=None, sorted_keys, sorted_vals, scene, prim_aabbs, root, layout)"""
+        n, off, noff = int(self.ranges["count"][m]), int(self.out_off[m]), int(self.node_off[m])
+        L, h = lib(), self.ctx.handle
+        nodes = np.empty(2 * n - 1, dtype=BVH2_NODE); boxes = np.empty(n, dtype=AABB); scene = np.empty(1, dtype=AABB)
+        _check(L.bvh_dev_download(h, nodes.ctypes.data, self.out.d_nodes + noff * 32, nodes.nbytes), "bvh_dev_download")
+        _check(L.bvh_dev_download(h, boxes.ctypes.data, self.out.d_prim_aabbs + off * 24, boxes.nbytes), "bvh_dev_download")
+        _check(L.bvh_dev_download(h, scene.ctypes.data, self.out.d_scene_extents + m * 24, scene.nbytes), "bvh_dev_download")
+        keys = vals = None
+        if self.out.d_sorted_keys:
+            keys = np.empty(n, dtype=np.uint32)
+            _check(L.bvh_dev_download(h, keys.ctypes.data, self.out.d_sorted_keys + off * 4, keys.nbytes), "bvh_dev_download")
+        if self.out.d_sorted_vals:
+            vals = np.empty(n, dtype=np.uint32)
+            _check(L.bvh_dev_download(h, vals.ctypes.data, self.out.d_sorted_vals + off * 4, vals.nbytes), "bvh_dev_download")
+        return {"nodes": nodes, "leaves": None, "sorted_keys": keys, "sorted_vals": vals, "scene": scene, "prim_aabbs": boxes, "root": int(self.roots()[m]), "layout": 0}
+
+    def download_all(self) -> dict:
+        """the six output arrays whole: dict(nodes, prim_aabbs, scenes, roots, sorted_keys, sorted_vals); slice them with out_off / node_off"""
+        L, h = lib(), self.ctx.handle
+
+        def get(ptr, dtype, count):
+            a = np.empty(count, dtype=dtype)
+            _check(L.bvh_dev_download(h, a.ctypes.data, ptr, a.nbytes), "bvh_dev_download")
+            return a
+        return {"nodes": get(self.out.d_nodes, BVH2_NODE, 2 * self.total - self.n_meshes), "prim_aabbs": get(self.out.d_prim_aabbs, AABB, self.total),
+                "scenes": get(self.out.d_scene_extents, AABB, self.n_meshes), "roots": get(self.out.d_roots, np.uint32, self.n_meshes),
+                "sorted_keys": get(self.out.d_sorted_keys, np.uint32, self.total) if self.out.d_sorted_keys else None,
+                "sorted_vals": get(self.out.d_sorted_vals, np.uint32, self.total) if self.out.d_sorted_vals else None}
+
+    def free(self) -> None:
+        for b in self._buffers:
+            b.free()
+        self._buffers = []
+
+
+def _many_host_input(meshes, tri_format):
+    """a list of host TRIANGLE arrays -> (host arrays of the chosen format, ranges, n_tris).  PACKED36 pads every mesh to a multiple of 4 records."""
+    for t in meshes:
+        if not isinstance(t, np.ndarray) or t.dtype != TRIANGLE:
+            raise BvhError("meshes must be host arrays of dtype TRIANGLE (64-byte records)")
+    counts = [len(t) for t in meshes]
+    if tri_format == TRI_PACKED36:
+        firsts, at = [], 0
+        for c in counts:
+            firsts.append(at); at += (c + 3) // 4 * 4
+        n_tris = at
+        flat = np.zeros((max(n_tris, 1), 9), dtype=np.float32)
+        for f, t in zip(firsts, meshes):
+            flat[f:f + len(t)] = np.concatenate([t["v1"], t["v2"], t["v3"]], axis=1)
+        return {"tris": flat}, np.array(list(zip(firsts, counts)), dtype=np.int64).reshape(-1, 2), n_tris
+    allt = np.concatenate(meshes) if meshes else np.zeros(0, dtype=TRIANGLE)
+    firsts = np.concatenate([[0], np.cumsum(counts)[:-1]]) if counts else []
+    ranges = np.array(list(zip(firsts, counts)), dtype=np.int64).reshape(-1, 2)
+    if tri_format == TRI_INDEXED:
+        verts = np.stack([allt["v1"], allt["v2"], allt["v3"]], axis=1).reshape(-1, 3).astype(np.float32)
+        return {"vertices": verts, "indices": np.arange(3 * len(allt), dtype=np.uint32)}, ranges, len(allt)
+    return {"tris": np.ascontiguousarray(allt)}, ranges, len(allt)
 
 
 class Context:
@@ -403,6 +559,49 @@ class Context:
                 for bfr in (offsets, boxes, prims):
                     if bfr is not None:
                         bfr.free()
+
+    def build_many(self, meshes, algo: int = ALGO_TWOPASS, tri_format: int = TRI_PADDED64, vertices=None, indices=None, n_vertices: int = 0,
+                   n_tris: int | None = None, sorted_arrays: bool = True) -> "ManyTrees":
+        """bvh_build_many: the LBVH of every mesh of a batch in one call.  ``meshes``: a list of host TRIANGLE arrays (concatenated, converted to ``tri_format`` and
+        uploaded), or a pair (tris, ranges) — ``tris`` one host TRIANGLE array (uploaded as PADDED64) or a device buffer in ``tri_format`` (None for INDEXED, whose
+        device ``vertices`` / ``indices`` / ``n_vertices`` are keyword arguments; ``n_tris`` = records / index triples in the buffers), ``ranges`` rows of
+        (first, count) or a MESH_RANGE array.  algo ALGO_TWOPASS (every root 0) or ALGO_SINGLEPASS.  Returns a ManyTrees that owns the output buffers."""
+        if algo not in (ALGO_TWOPASS, ALGO_SINGLEPASS):
+            raise BvhError("build_many builds LBVH trees: algo ALGO_TWOPASS or ALGO_SINGLEPASS")
+        keep = []
+        try:
+            if isinstance(meshes, tuple):
+                tris, ranges = meshes
+                if isinstance(tris, np.ndarray):
+                    if tris.dtype != TRIANGLE:
+                        raise BvhError("tris must have dtype TRIANGLE (64-byte records)")
+                    n_tris, tri_format = len(tris), TRI_PADDED64
+                    tris = self.upload(np.ascontiguousarray(tris)); keep.append(tris)
+                elif n_tris is None:
+                    raise BvhError("n_tris is required for device inputs")
+            else:
+                host, ranges, n_tris = _many_host_input(list(meshes), tri_format)
+                bufs = {k: self.upload(v) for k, v in host.items()}
+                keep.extend(bufs.values())
+                tris, vertices, indices = bufs.get("tris"), bufs.get("vertices"), bufs.get("indices")
+                if tri_format == TRI_INDEXED:
+                    n_vertices = len(host["vertices"])
+            ranges = many_check_ranges(ranges, n_tris, tri_format)
+            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                             _ptr(indices) if indices is not None else None, n_vertices, 0)
+            _, _, total = many_layout(ranges["count"])
+            n = len(ranges)
+            outs = [self.alloc((2 * total - n) * 32), self.alloc(total * 24), self.alloc(n * 24), self.alloc(n * 4),
+                    self.alloc(total * 4) if sorted_arrays else None, self.alloc(total * 4) if sorted_arrays else None]
+            keep.extend(b for b in outs if b is not None)
+            out = ManyOut(*[b.ptr if b is not None else None for b in outs])
+            mt = ManyTrees(self, algo, inp, n_tris, ranges, out, keep)
+            _check(lib().bvh_build_many(self.handle, int(algo), C.byref(inp), n_tris, ranges.ctypes.data, n, C.byref(out), C.byref(mt.timings)), "bvh_build_many")
+            keep = []
+            return mt
+        finally:
+            for b in keep:
+                b.free()
 
     def close(self) -> None:
         if self.handle:

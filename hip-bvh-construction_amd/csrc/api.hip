@@ -100,6 +100,12 @@ struct bvh_ctx {
     // u64 scan sums[OVERLAP_SCAN_BLOCKS] | u32 heavy list[split_cap].  Calls on the ctx's stream are ordered, so one set serves them all
     char* split_words = nullptr;
     uint32_t split_cap = 0;
+    // bvh_build_many's item table, outside the arena (the call may not touch it): uint4 {first, count, out_off, mesh} per mesh, binned by size class.  The host fills the
+    // pinned copy and an asynchronous copy on the stream brings it over; many_ev marks the end of that copy, so the next call knows when it may refill the pinned words
+    uint4* many_items = nullptr;
+    uint4* many_host = nullptr;
+    uint32_t many_cap = 0;
+    hipEvent_t many_ev = nullptr;
 };
 
 // bvh_scene: device memory of its own (one allocation, carved as below), outside the ctx's arena; only the top-level build uses the arena
@@ -401,7 +407,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); }); }
     *out = c;
     return 0;
 }
@@ -415,6 +421,9 @@ void bvh_ctx_destroy(bvh_ctx* c) {
     if (c->tris) hipFree(c->tris);
     if (c->subset_words) hipFree(c->subset_words);
     if (c->split_words) hipFree(c->split_words);
+    if (c->many_items) hipFree(c->many_items);
+    if (c->many_host) hipHostFree(c->many_host);
+    if (c->many_ev) hipEventDestroy(c->many_ev);
     for (auto& e : c->ev) if (e) hipEventDestroy(e);
     if (c->h_pinned) hipHostFree(c->h_pinned);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -1192,6 +1201,152 @@ int bvh_split_refs(bvh_ctx* c, const bvh_build_input* in, uint32_t n, float sa_m
         *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
         if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
     }
+    return 0;
+}
+
+// ---- batched small-mesh builds (no working counterpart in the reference: src/BatchedBuildKernel.h:218-312 is what this was meant to be) ------------------------------
+static_assert(MANY_MAX == BVH_MANY_LDS_MAX_PRIMS, "kernels.hpp MANY_MAX is the header's BVH_MANY_LDS_MAX_PRIMS");
+namespace {
+struct ManyLayout { uint64_t total = 0; uint32_t n_class[4] = {0, 0, 0, 0}; uint32_t n_large = 0, max_large = 0; };
+inline int many_class(uint32_t count) { return count <= 64u ? 0 : count <= 128u ? 1 : count <= 256u ? 2 : count <= (uint32_t)MANY_MAX ? 3 : 4; }
+inline bool many_algo_ok(bvh_algo algo) { return algo == BVH_LBVH_SINGLEPASS || algo == BVH_LBVH_TWOPASS; }
+// the checks bvh_build_many and bvh_many_tree share: arguments, format, ranges
+int many_check(bvh_algo algo, const bvh_build_input* in, uint32_t n_tris, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_out* out, ManyLayout* lay) {
+    if (!in || !h_meshes || !out || n_meshes == 0 || !many_algo_ok(algo)) return BVH_E_INVALID_ARG;
+    if (in->morton_bits != 30 || stage_extents_valid(in)) return BVH_E_INVALID_ARG;
+    if (!out->d_nodes || !out->d_prim_aabbs || !out->d_scene_extents || !out->d_roots) return BVH_E_INVALID_ARG;
+    ManyLayout l;
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        const uint32_t first = h_meshes[m].first, count = h_meshes[m].count;
+        if (count < 2 || (uint64_t)first + count > (uint64_t)n_tris) return BVH_E_INVALID_ARG;
+        if (in->tri_format == BVH_TRI_PACKED36 && (first & 3u)) return BVH_E_INVALID_ARG;      // (a consumer reads the slice's records with 16-byte loads)
+        l.total += count;
+        if (l.total >= (1ull << 30)) return BVH_E_INVALID_ARG;
+        const int k = many_class(count);
+        if (k < 4) ++l.n_class[k]; else { ++l.n_large; if (count > l.max_large) l.max_large = count; }
+    }
+    if (lay) *lay = l;
+    return 0;
+}
+} // namespace
+
+int bvh_build_many(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_t n_tris, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_out* out,
+                   bvh_timings* tm) {
+    if (!c) return BVH_E_INVALID_ARG;
+    ManyLayout lay;
+    int r = many_check(algo, in, n_tris, h_meshes, n_meshes, out, &lay); if (r) return r;
+    {   // the output arrays may overlap neither each other nor the input
+        struct Range { uintptr_t lo, hi; };
+        auto range = [](const void* p, uint64_t bytes) { return Range{ (uintptr_t)p, (uintptr_t)p + (p ? bytes : 0u) }; };
+        const Range rs[8] = {
+            range(out->d_nodes, (2ull * lay.total - n_meshes) * sizeof(bvh2_node)), range(out->d_prim_aabbs, lay.total * sizeof(bvh_aabb)),
+            range(out->d_scene_extents, (uint64_t)n_meshes * sizeof(bvh_aabb)), range(out->d_roots, (uint64_t)n_meshes * sizeof(u32)),
+            range(out->d_sorted_keys, lay.total * sizeof(u32)), range(out->d_sorted_vals, lay.total * sizeof(u32)),
+            in->tri_format == BVH_TRI_INDEXED ? range(in->d_vertices, (uint64_t)in->n_vertices * 12u) : range(in->d_tris, (uint64_t)n_tris * (in->tri_format == BVH_TRI_PADDED64 ? 64u : 36u)),
+            in->tri_format == BVH_TRI_INDEXED ? range(in->d_indices, (uint64_t)n_tris * 12u) : Range{ 0, 0 } };
+        for (int a = 0; a < 6; ++a)
+            for (int b = a + 1; b < 8; ++b)
+                if (rs[a].lo < rs[a].hi && rs[b].lo < rs[b].hi && rs[a].lo < rs[b].hi && rs[b].lo < rs[a].hi) return BVH_E_INVALID_ARG;
+    }
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    const uint32_t n_small = n_meshes - lay.n_large;
+    if (n_small > c->many_cap) {                              // (grown outside the arena; the old table may still be read by a launch on the stream)
+        uint4* d = nullptr; uint4* h = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), (size_t)n_small * sizeof(uint4)));
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&h), (size_t)n_small * sizeof(uint4), hipHostMallocDefault);
+        if (e == hipSuccess && !c->many_ev) e = hipEventCreateWithFlags(&c->many_ev, hipEventDisableTiming);
+        if (e == hipSuccess && c->many_items) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hipFree(d); if (h) (void)hipHostFree(h); return -(int)e; }
+        if (c->many_items) { (void)hipFree(c->many_items); (void)hipHostFree(c->many_host); }
+        c->many_items = d; c->many_host = h; c->many_cap = n_small;
+    } else if (n_small) HIP_TRY(hipEventSynchronize(c->many_ev));   // the previous call's copy has read the pinned words
+    if (lay.n_large) { r = ensure_capacity(c, lay.max_large); if (r) return r; }
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    const bool prof = c->profiling && sampled;
+    if (prof) HIP_TRY(hipEventRecord(c->ev[5], s));
+    const bool karras = algo == BVH_LBVH_TWOPASS;
+    if (n_small) {
+        uint32_t at[4] = { 0u, lay.n_class[0], lay.n_class[0] + lay.n_class[1], lay.n_class[0] + lay.n_class[1] + lay.n_class[2] };
+        uint32_t off = 0;
+        for (uint32_t m = 0; m < n_meshes; ++m) {
+            const int k = many_class(h_meshes[m].count);
+            if (k < 4) c->many_host[at[k]++] = make_uint4(h_meshes[m].first, h_meshes[m].count, off, m);
+            off += h_meshes[m].count;
+        }
+        HIP_TRY(hipMemcpyAsync(c->many_items, c->many_host, (size_t)n_small * sizeof(uint4), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(c->many_ev, s));
+        struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+        ManyArgs a;
+        a.tris = in->d_tris; a.verts = in->d_vertices; a.idx = in->d_indices; a.n_verts = in->n_vertices;
+        a.boxes = static_cast<bvh_aabb*>(out->d_prim_aabbs); a.scenes = static_cast<bvh_aabb*>(out->d_scene_extents); a.nodes = static_cast<bvh2_node*>(out->d_nodes);
+        a.roots = out->d_roots; a.skeys = out->d_sorted_keys; a.svals = out->d_sorted_vals;
+        launch_many(s, a, (int)in->tri_format, karras, c->many_items, lay.n_class);
+        HIP_TRY(hipGetLastError());
+        if (install.on) c->recorder.mark(s, nullptr);
+    }
+    if (lay.n_large) {                                        // the ordinary build on the ctx (its arena, its read-backs), one mesh after another, copied to the slice
+        uint32_t off = 0;
+        for (uint32_t m = 0; m < n_meshes; ++m) {
+            const uint32_t first = h_meshes[m].first, count = h_meshes[m].count;
+            if (many_class(count) == 4) {
+                bvh_build_input sub = *in;
+                if (in->tri_format == BVH_TRI_INDEXED) sub.d_indices = static_cast<const char*>(in->d_indices) + 12ull * first;
+                else sub.d_tris = static_cast<const char*>(in->d_tris) + (in->tri_format == BVH_TRI_PADDED64 ? 64ull : 36ull) * first;
+                bvh_result t;
+                r = build_impl(c, algo, &sub, count, &t, nullptr); if (r) return r;
+                launch_copy_bytes(s, static_cast<char*>(out->d_nodes) + (2ull * off - m) * sizeof(bvh2_node), t.d_nodes, (2ull * count - 1u) * sizeof(bvh2_node));
+                launch_copy_bytes(s, static_cast<char*>(out->d_prim_aabbs) + (uint64_t)off * sizeof(bvh_aabb), t.d_prim_aabbs, (uint64_t)count * sizeof(bvh_aabb));
+                launch_copy_bytes(s, static_cast<char*>(out->d_scene_extents) + (uint64_t)m * sizeof(bvh_aabb), t.d_scene_extent, sizeof(bvh_aabb));
+                if (out->d_sorted_keys) launch_copy_bytes(s, out->d_sorted_keys + off, t.d_sorted_keys, (uint64_t)count * sizeof(u32));
+                if (out->d_sorted_vals) launch_copy_bytes(s, out->d_sorted_vals + off, t.d_sorted_vals, (uint64_t)count * sizeof(u32));
+                if (karras) HIP_TRY(hipMemsetAsync(out->d_roots + m, 0, sizeof(u32), s));
+                else launch_copy_bytes(s, out->d_roots + m, c->small, sizeof(u32));
+                HIP_TRY(hipGetLastError());
+            }
+            off += count;
+        }
+    }
+    if (prof) HIP_TRY(hipEventRecord(c->ev[6], s));
+    if (tm) {
+        std::memset(tm, 0, sizeof *tm);
+        tm->bytes_algorithmic = algorithmic_bytes(algo, (uint32_t)lay.total);
+        tm->sampled = prof ? 1u : 0u;
+        if (prof) {
+            HIP_TRY(hipEventSynchronize(c->ev[6]));
+            HIP_TRY(hipEventElapsedTime(&tm->ms_build, c->ev[5], c->ev[6]));
+            tm->ms_total = tm->ms_build;
+        }
+    }
+    return 0;
+}
+
+int bvh_many_tree(bvh_algo algo, const bvh_build_input* in, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_out* out, uint32_t m,
+                  const uint32_t* h_roots, bvh_result* tree_out, bvh_build_input* tris_out) {
+    if (!in || !h_meshes || !out || !tree_out || !tris_out || m >= n_meshes || !many_algo_ok(algo)) return BVH_E_INVALID_ARG;
+    if (algo == BVH_LBVH_SINGLEPASS && !h_roots) return BVH_E_INVALID_ARG;
+    if (in->morton_bits != 30 || stage_extents_valid(in)) return BVH_E_INVALID_ARG;
+    if (!out->d_nodes || !out->d_prim_aabbs || !out->d_scene_extents) return BVH_E_INVALID_ARG;
+    uint64_t off = 0;
+    for (uint32_t k = 0; k < m; ++k) off += h_meshes[k].count;
+    const uint32_t first = h_meshes[m].first, count = h_meshes[m].count;
+    if (count < 2 || off + count >= (1ull << 30)) return BVH_E_INVALID_ARG;
+    if (in->tri_format == BVH_TRI_PACKED36 && (first & 3u)) return BVH_E_INVALID_ARG;
+    bvh_result t; std::memset(&t, 0, sizeof t);
+    t.d_nodes = static_cast<char*>(out->d_nodes) + (2ull * off - m) * sizeof(bvh2_node);
+    t.d_prim_aabbs = static_cast<char*>(out->d_prim_aabbs) + off * sizeof(bvh_aabb);
+    t.d_scene_extent = static_cast<char*>(out->d_scene_extents) + (uint64_t)m * sizeof(bvh_aabb);
+    t.d_sorted_keys = out->d_sorted_keys ? out->d_sorted_keys + off : nullptr;
+    t.d_sorted_vals = out->d_sorted_vals ? out->d_sorted_vals + off : nullptr;
+    t.root = algo == BVH_LBVH_TWOPASS ? 0u : h_roots[m];
+    t.n_internal = count - 1; t.n_leaves = count; t.layout = 0; t.key_bits = 32;
+    bvh_build_input ti = *in;
+    switch (in->tri_format) {
+        case BVH_TRI_PADDED64: ti.d_tris = static_cast<const char*>(in->d_tris) + 64ull * first; t.d_tris = ti.d_tris; break;
+        case BVH_TRI_PACKED36: ti.d_tris = static_cast<const char*>(in->d_tris) + 36ull * first; break;
+        default:               ti.d_indices = static_cast<const char*>(in->d_indices) + 12ull * first; break;
+    }
+    *tree_out = t; *tris_out = ti;
     return 0;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "bvh/types.h"
 
 namespace bvh {
 
@@ -239,6 +240,15 @@ void launch_split_fill(hipStream_t s, int tri_format, const void* d_tris, const 
                        const uint64_t* d_total, const uint32_t* d_heavy_list, const uint32_t* d_heavy_count);
 void launch_remap_leaves(hipStream_t s, void* d_nodes, void* d_leaves, int layout, uint32_t n, const uint32_t* d_map, uint32_t n_map);
 
+// ---- batched small-mesh builds (many.hip): bvh_build_many's kernels.  ManyArgs: the validated input (a bvh_build_input's fields) and the output arrays of a
+// bvh_many_out (skeys / svals may be null).  launch_many: k_many_wave (meshes of at most 64 triangles, one wave each) and k_many_block (at most 128 / 256 /
+// MANY_MAX triangles, one workgroup each) over d_items, uint4 {first, count, out_off, mesh} records binned by size class: n_class[0..3] of each, in that order.
+// karras: the two-pass builder's node numbering instead of the single-pass one (lbvh.hip)
+constexpr int MANY_MAX = 512;                                // BVH_MANY_LDS_MAX_PRIMS (api.hip asserts it)
+struct ManyArgs { const void* tris; const void* verts; const void* idx; uint32_t n_verts; bvh_aabb* boxes; bvh_aabb* scenes; bvh2_node* nodes; uint32_t* roots;
+                  uint32_t* skeys; uint32_t* svals; };
+void launch_many(hipStream_t s, const ManyArgs& a, int tri_format, bool karras, const void* d_items, const uint32_t n_class[4]);
+
 // ---- instanced scenes (scene.hip): bvh_scene's kernels.  SceneBlas: the device copy of one validated bvh_blas (64 bytes, read whole when a ray enters an
 // instance); tris = Triangle[n] / float[9n] / the vertices of INDEXED input, idx = INDEXED indices, parent = the BLAS's k_refit_plan plan (u32[2n-1]).
 struct SceneBlas { const void* nodes; const void* leaves; const void* tris; const void* idx; const uint32_t* parent; uint32_t n, root, layout, fmt, nv, pad; };
@@ -285,6 +295,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many();
 
 } // namespace bvh

@@ -164,6 +164,48 @@ int  bvh_stage_morton_plan(bvh_ctx* ctx, const void* d_scene_extent, int total_b
 int  bvh_sort_pairs64(bvh_ctx* ctx, const uint64_t* d_keys_in, const uint32_t* d_vals_in, uint32_t n,
                       uint64_t* d_keys_out, uint32_t* d_vals_out, int start_bit, int end_bit);
 
+/* ---- many small meshes in one call (what the reference's BatchedBuildKernelLbvh, src/BatchedBuildKernel.h:218-312, was meant to be) ---------
+ * The bottom-level trees of an instanced scene — thousands of meshes of tens to hundreds of triangles — built by one call instead of one bvh_build_ex each
+ * (which costs ~0.1 ms of launch latency per mesh whatever its size).  Mesh m is triangles [first, first + count) of the input arrays; every mesh's arrays land
+ * in a slice of six caller-owned device arrays.  out_off[m] = the sum of the counts of meshes 0 .. m-1, total = the sum of all counts (host arithmetic).
+ * algo: BVH_LBVH_SINGLEPASS or BVH_LBVH_TWOPASS (two-pass: every root is 0, so a host can fill every bvh_result without a read-back); anything else is
+ * BVH_E_INVALID_ARG — a batched PLOC-family emit is a later step.  in->morton_bits must be 30.
+ * Formats: all three.  PADDED64 / PACKED36: mesh m reads records first .. first+count of d_tris; INDEXED: index triples first .. first+count of d_indices over the
+ * shared d_vertices.  Leaf primitive indices and d_sorted_vals are mesh-local, 0 .. count-1.
+ * bvh_many_tree (host arithmetic only, no device work) describes mesh m's slice as a bvh_result (layout 0, key_bits 32, d_leaves / d_morton_keys NULL) plus the
+ * bvh_build_input that names its triangles, ready for bvh_intersect / bvh_closest_point / bvh_refit_ex / a bvh_blas: PADDED64 tree_out->d_tris = d_tris + 64*first
+ * (tris_out names the same); PACKED36 tree_out->d_tris NULL and tris_out->d_tris = d_tris + 36*first — consumers need that 16-byte aligned, so bvh_build_many
+ * itself rejects first % 4 != 0 for this format; INDEXED tree_out->d_tris NULL and tris_out->d_indices = d_indices + 3*first over the same vertices.
+ * Identity: for every mesh the bytes of its node slice, its d_prim_aabbs slice, its root and its d_sorted_keys / d_sorted_vals slices equal what
+ * bvh_build_ex(ctx2, algo, tris_out, count) produces; its scene extent compares equal and is byte-equal unless a coordinate is a zero of mixed sign (as for
+ * bvh_refit_subset).  The bytes depend on neither the internal path that served the mesh, nor the other meshes of the batch, nor the call: sorted order is ascending
+ * {key, mesh-local index} (the pipeline's stable 32-bit sort, codes with bits 30 / 31 set included); an internal box is the fminf / fmaxf union of the leaf boxes of
+ * its range (every union order gives the same bits, mixed-sign zeros apart); nodes are numbered as the LBVH builders number them.
+ * Paths: count <= 64: one wave per mesh, several meshes per workgroup; 65 .. BVH_MANY_LDS_MAX_PRIMS: one workgroup per mesh, extent, codes, sort and emit in LDS;
+ * larger: the ordinary bvh_build_ex on the ctx, one mesh after another, its arrays copied to the slice — ONLY then the call counts as a build on the ctx (it
+ * invalidates results that live in the ctx's arena and may re-allocate it) and waits for what such a build waits for.  The host bins the meshes by size, which is
+ * why the ranges are host memory; they are read before the call returns.  No kernel waits on another wave or workgroup.
+ * Nothing but the slices is written; the arena is untouched unless the large-mesh path runs.  Asynchronous on the ctx's stream apart from that path and from what
+ * the timings need (profiling on: ms_build = ms_total = the whole call).  bvh_ctx_kernel_times reports k_many_wave and k_many_block.
+ * Errors (BVH_E_INVALID_ARG, nothing is written or enqueued): NULL ctx / in / h_meshes / out, NULL d_nodes / d_prim_aabbs / d_scene_extents / d_roots, a format error
+ * as in bvh_build_ex, morton_bits != 30, n_meshes == 0, a count < 2, first + count > n_tris, total >= 2^30, a misaligned PACKED36 first, output arrays overlapping
+ * each other or the input; bvh_many_tree: m >= n_meshes, NULL h_roots for single-pass, NULL tree_out / tris_out. */
+#define BVH_MANY_LDS_MAX_PRIMS 512          /* meshes up to this size are built in LDS by the batched kernels */
+typedef struct { uint32_t first, count; } bvh_mesh_range;   /* triangles [first, first+count) of the input arrays */
+typedef struct {
+    void*     d_nodes;          /* Bvh2Node[2*total - n_meshes]; mesh m's LBVH-layout array (2*count-1 records) starts at record 2*out_off[m] - m */
+    void*     d_prim_aabbs;     /* bvh_aabb[total];   mesh m's at out_off[m], by mesh-local primitive index */
+    void*     d_scene_extents;  /* bvh_aabb[n_meshes] */
+    uint32_t* d_roots;          /* u32[n_meshes]: mesh-local root (two-pass: 0) */
+    uint32_t* d_sorted_keys;    /* u32[total] or NULL */
+    uint32_t* d_sorted_vals;    /* u32[total] or NULL (mesh-local indices) */
+} bvh_many_out;
+int  bvh_build_many(bvh_ctx* ctx, bvh_algo algo, const bvh_build_input* in, uint32_t n_tris,
+                    const bvh_mesh_range* h_meshes /* host */, uint32_t n_meshes, const bvh_many_out* out, bvh_timings* timings /* may be NULL */);
+/* host arithmetic only, no device work: mesh m's slice as a caller-filled bvh_result + the bvh_build_input that names its triangles */
+int  bvh_many_tree(bvh_algo algo, const bvh_build_input* in, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_out* out,
+                   uint32_t m, const uint32_t* h_roots /* NULL allowed for BVH_LBVH_TWOPASS: root 0 */, bvh_result* tree_out, bvh_build_input* tris_out);
+
 /* ---- refit (no counterpart in the reference) ------------------------------------------------------------------------------------------
  * Recompute every box of an existing tree from new triangle positions, with the topology kept (deforming / animated meshes: vertices move, connectivity
  * and ordering stay).  Stage E, then the boxes are unioned bottom-up through the existing child links; Morton codes, sort and hierarchy search are skipped.
