@@ -77,7 +77,7 @@ EXPORTS = [
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
-    "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree",
+    "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
 
 
@@ -134,6 +134,12 @@ class BuildInput(C.Structure):
 class ManyOut(C.Structure):
     """bvh_many_out: the six caller-owned output arrays of bvh_build_many"""
     _fields_ = [("d_nodes", C.c_void_p), ("d_prim_aabbs", C.c_void_p), ("d_scene_extents", C.c_void_p), ("d_roots", C.c_void_p),
+                ("d_sorted_keys", C.c_void_p), ("d_sorted_vals", C.c_void_p)]
+
+
+class ManyPlocOut(C.Structure):
+    """bvh_many_ploc_out: the six caller-owned output arrays of bvh_build_many_ploc"""
+    _fields_ = [("d_nodes", C.c_void_p), ("d_leaves", C.c_void_p), ("d_prim_aabbs", C.c_void_p), ("d_scene_extents", C.c_void_p),
                 ("d_sorted_keys", C.c_void_p), ("d_sorted_vals", C.c_void_p)]
 
 
@@ -229,6 +235,8 @@ def lib() -> C.CDLL:
         "bvh_remap_leaves": ([vp, C.POINTER(Result), vp, u32], i32),
         "bvh_build_many": ([vp, i32, C.POINTER(BuildInput), u32, vp, u32, C.POINTER(ManyOut), C.POINTER(Timings)], i32),
         "bvh_many_tree": ([i32, C.POINTER(BuildInput), vp, u32, C.POINTER(ManyOut), u32, vp, C.POINTER(Result), C.POINTER(BuildInput)], i32),
+        "bvh_build_many_ploc": ([vp, i32, C.POINTER(BuildInput), u32, vp, u32, C.POINTER(ManyPlocOut), C.POINTER(Timings)], i32),
+        "bvh_many_ploc_tree": ([i32, C.POINTER(BuildInput), vp, u32, C.POINTER(ManyPlocOut), u32, C.POINTER(Result), C.POINTER(BuildInput)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -300,6 +308,13 @@ def many_layout(counts):
     out_off = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64) if len(counts) else np.zeros(0, np.int64)
     node_off = 2 * out_off - np.arange(len(counts), dtype=np.int64)
     return out_off, node_off, int(counts.sum())
+
+
+def many_ploc_layout(counts):
+    """bvh_build_many_ploc's output layout: (out_off, node_off, total) — mesh m's d_leaves / d_prim_aabbs / d_sorted_* slices start at out_off[m] (the exclusive
+    scan of the counts), its count-1 node records at record node_off[m] = out_off[m] - m; total = the sum of the counts."""
+    out_off, _, total = many_layout(counts)
+    return out_off, out_off - np.arange(len(out_off), dtype=np.int64), total
 
 
 def many_check_ranges(ranges, n_tris: int, tri_format: int = TRI_PADDED64) -> np.ndarray:
@@ -411,6 +426,48 @@ class ManyTrees:
         for b in self._buffers:
             b.free()
         self._buffers = []
+
+
+class ManyPlocTrees(ManyTrees):
+    """The trees of one Context.build_many_ploc call: ManyTrees' surface over PLOC-layout slices (n-1 nodes + n PrimRef leaves per mesh, every root 0)."""
+
+    def __init__(self, ctx, inp, n_tris, ranges, out, buffers):
+        super().__init__(ctx, ALGO_PLOCPP, inp, n_tris, ranges, out, buffers)
+        self.out_off, self.node_off, self.total = many_ploc_layout(ranges["count"])
+
+    def roots(self) -> np.ndarray:
+        """u32[n_meshes]: all 0 (no read-back)"""
+        if self._roots is None:
+            self._roots = np.zeros(self.n_meshes, dtype=np.uint32)
+        return self._roots
+
+    def _slice(self, m: int):
+        r, t = Result(), BuildInput()
+        _check(lib().bvh_many_ploc_tree(self.algo, C.byref(self.input), self.ranges.ctypes.data, self.n_meshes, C.byref(self.out), int(m), C.byref(r), C.byref(t)),
+               "bvh_many_ploc_tree")
+        return r, t
+
+    def _get(self, ptr, dtype, count):
+        a = np.empty(count, dtype=dtype)
+        _check(lib().bvh_dev_download(self.ctx.handle, a.ctypes.data, ptr, a.nbytes), "bvh_dev_download")
+        return a
+
+    def download(self, m: int) -> dict:
+        """mesh m's arrays as numpy: dict(nodes, leaves, sorted_keys, sorted_vals, scene, prim_aabbs, root, layout)"""
+        n, off, noff = int(self.ranges["count"][m]), int(self.out_off[m]), int(self.node_off[m])
+        o = self.out
+        return {"nodes": self._get(o.d_nodes + noff * 32, BVH2_NODE, n - 1), "leaves": self._get(o.d_leaves + off * 28, PRIMREF, n),
+                "sorted_keys": self._get(o.d_sorted_keys + off * 4, np.uint32, n) if o.d_sorted_keys else None,
+                "sorted_vals": self._get(o.d_sorted_vals + off * 4, np.uint32, n) if o.d_sorted_vals else None,
+                "scene": self._get(o.d_scene_extents + m * 24, AABB, 1), "prim_aabbs": self._get(o.d_prim_aabbs + off * 24, AABB, n), "root": 0, "layout": 1}
+
+    def download_all(self) -> dict:
+        """the six output arrays whole: dict(nodes, leaves, prim_aabbs, scenes, sorted_keys, sorted_vals); slice them with out_off / node_off"""
+        o = self.out
+        return {"nodes": self._get(o.d_nodes, BVH2_NODE, self.total - self.n_meshes), "leaves": self._get(o.d_leaves, PRIMREF, self.total),
+                "prim_aabbs": self._get(o.d_prim_aabbs, AABB, self.total), "scenes": self._get(o.d_scene_extents, AABB, self.n_meshes),
+                "sorted_keys": self._get(o.d_sorted_keys, np.uint32, self.total) if o.d_sorted_keys else None,
+                "sorted_vals": self._get(o.d_sorted_vals, np.uint32, self.total) if o.d_sorted_vals else None}
 
 
 def _many_host_input(meshes, tri_format):
@@ -560,6 +617,29 @@ class Context:
                     if bfr is not None:
                         bfr.free()
 
+    def _many_input(self, meshes, tri_format, vertices, indices, n_vertices, n_tris, keep):
+        """build_many's / build_many_ploc's input conventions -> (BuildInput, MESH_RANGE array, n_tris); what it uploads is appended to ``keep``"""
+        if isinstance(meshes, tuple):
+            tris, ranges = meshes
+            if isinstance(tris, np.ndarray):
+                if tris.dtype != TRIANGLE:
+                    raise BvhError("tris must have dtype TRIANGLE (64-byte records)")
+                n_tris, tri_format = len(tris), TRI_PADDED64
+                tris = self.upload(np.ascontiguousarray(tris)); keep.append(tris)
+            elif n_tris is None:
+                raise BvhError("n_tris is required for device inputs")
+        else:
+            host, ranges, n_tris = _many_host_input(list(meshes), tri_format)
+            bufs = {k: self.upload(v) for k, v in host.items()}
+            keep.extend(bufs.values())
+            tris, vertices, indices = bufs.get("tris"), bufs.get("vertices"), bufs.get("indices")
+            if tri_format == TRI_INDEXED:
+                n_vertices = len(host["vertices"])
+        ranges = many_check_ranges(ranges, n_tris, tri_format)
+        inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                         _ptr(indices) if indices is not None else None, n_vertices, 0)
+        return inp, ranges, n_tris
+
     def build_many(self, meshes, algo: int = ALGO_TWOPASS, tri_format: int = TRI_PADDED64, vertices=None, indices=None, n_vertices: int = 0,
                    n_tris: int | None = None, sorted_arrays: bool = True) -> "ManyTrees":
         """bvh_build_many: the LBVH of every mesh of a batch in one call.  ``meshes``: a list of host TRIANGLE arrays (concatenated, converted to ``tri_format`` and
@@ -567,28 +647,10 @@ class Context:
         device ``vertices`` / ``indices`` / ``n_vertices`` are keyword arguments; ``n_tris`` = records / index triples in the buffers), ``ranges`` rows of
         (first, count) or a MESH_RANGE array.  algo ALGO_TWOPASS (every root 0) or ALGO_SINGLEPASS.  Returns a ManyTrees that owns the output buffers."""
         if algo not in (ALGO_TWOPASS, ALGO_SINGLEPASS):
-            raise BvhError("build_many builds LBVH trees: algo ALGO_TWOPASS or ALGO_SINGLEPASS")
+            raise BvhError("build_many builds LBVH trees: algo ALGO_TWOPASS or ALGO_SINGLEPASS (PLOC++ trees: build_many_ploc)")
         keep = []
         try:
-            if isinstance(meshes, tuple):
-                tris, ranges = meshes
-                if isinstance(tris, np.ndarray):
-                    if tris.dtype != TRIANGLE:
-                        raise BvhError("tris must have dtype TRIANGLE (64-byte records)")
-                    n_tris, tri_format = len(tris), TRI_PADDED64
-                    tris = self.upload(np.ascontiguousarray(tris)); keep.append(tris)
-                elif n_tris is None:
-                    raise BvhError("n_tris is required for device inputs")
-            else:
-                host, ranges, n_tris = _many_host_input(list(meshes), tri_format)
-                bufs = {k: self.upload(v) for k, v in host.items()}
-                keep.extend(bufs.values())
-                tris, vertices, indices = bufs.get("tris"), bufs.get("vertices"), bufs.get("indices")
-                if tri_format == TRI_INDEXED:
-                    n_vertices = len(host["vertices"])
-            ranges = many_check_ranges(ranges, n_tris, tri_format)
-            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                             _ptr(indices) if indices is not None else None, n_vertices, 0)
+            inp, ranges, n_tris = self._many_input(meshes, tri_format, vertices, indices, n_vertices, n_tris, keep)
             _, _, total = many_layout(ranges["count"])
             n = len(ranges)
             outs = [self.alloc((2 * total - n) * 32), self.alloc(total * 24), self.alloc(n * 24), self.alloc(n * 4),
@@ -597,6 +659,28 @@ class Context:
             out = ManyOut(*[b.ptr if b is not None else None for b in outs])
             mt = ManyTrees(self, algo, inp, n_tris, ranges, out, keep)
             _check(lib().bvh_build_many(self.handle, int(algo), C.byref(inp), n_tris, ranges.ctypes.data, n, C.byref(out), C.byref(mt.timings)), "bvh_build_many")
+            keep = []
+            return mt
+        finally:
+            for b in keep:
+                b.free()
+
+    def build_many_ploc(self, meshes, tri_format: int = TRI_PADDED64, vertices=None, indices=None, n_vertices: int = 0, n_tris: int | None = None,
+                        sorted_arrays: bool = True) -> "ManyPlocTrees":
+        """bvh_build_many_ploc: the PLOC++ tree of every mesh of a batch in one call; input conventions as build_many.  Returns a ManyPlocTrees that owns the
+        output buffers."""
+        keep = []
+        try:
+            inp, ranges, n_tris = self._many_input(meshes, tri_format, vertices, indices, n_vertices, n_tris, keep)
+            _, _, total = many_ploc_layout(ranges["count"])
+            n = len(ranges)
+            outs = [self.alloc((total - n) * 32), self.alloc(total * 28), self.alloc(total * 24), self.alloc(n * 24),
+                    self.alloc(total * 4) if sorted_arrays else None, self.alloc(total * 4) if sorted_arrays else None]
+            keep.extend(b for b in outs if b is not None)
+            out = ManyPlocOut(*[b.ptr if b is not None else None for b in outs])
+            mt = ManyPlocTrees(self, inp, n_tris, ranges, out, keep)
+            _check(lib().bvh_build_many_ploc(self.handle, ALGO_PLOCPP, C.byref(inp), n_tris, ranges.ctypes.data, n, C.byref(out), C.byref(mt.timings)),
+                   "bvh_build_many_ploc")
             keep = []
             return mt
         finally:

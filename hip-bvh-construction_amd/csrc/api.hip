@@ -407,7 +407,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -1210,11 +1210,9 @@ namespace {
 struct ManyLayout { uint64_t total = 0; uint32_t n_class[4] = {0, 0, 0, 0}; uint32_t n_large = 0, max_large = 0; };
 inline int many_class(uint32_t count) { return count <= 64u ? 0 : count <= 128u ? 1 : count <= 256u ? 2 : count <= (uint32_t)MANY_MAX ? 3 : 4; }
 inline bool many_algo_ok(bvh_algo algo) { return algo == BVH_LBVH_SINGLEPASS || algo == BVH_LBVH_TWOPASS; }
-// the checks bvh_build_many and bvh_many_tree share: arguments, format, ranges
-int many_check(bvh_algo algo, const bvh_build_input* in, uint32_t n_tris, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_out* out, ManyLayout* lay) {
-    if (!in || !h_meshes || !out || n_meshes == 0 || !many_algo_ok(algo)) return BVH_E_INVALID_ARG;
-    if (in->morton_bits != 30 || stage_extents_valid(in)) return BVH_E_INVALID_ARG;
-    if (!out->d_nodes || !out->d_prim_aabbs || !out->d_scene_extents || !out->d_roots) return BVH_E_INVALID_ARG;
+// the input's part of the checks bvh_build_many, bvh_build_many_ploc and their *_tree calls share: format, ranges (in and h_meshes are not NULL)
+int many_check_input(const bvh_build_input* in, uint32_t n_tris, const bvh_mesh_range* h_meshes, uint32_t n_meshes, ManyLayout* lay) {
+    if (n_meshes == 0 || in->morton_bits != 30 || stage_extents_valid(in)) return BVH_E_INVALID_ARG;
     ManyLayout l;
     for (uint32_t m = 0; m < n_meshes; ++m) {
         const uint32_t first = h_meshes[m].first, count = h_meshes[m].count;
@@ -1228,26 +1226,35 @@ int many_check(bvh_algo algo, const bvh_build_input* in, uint32_t n_tris, const 
     if (lay) *lay = l;
     return 0;
 }
+int many_check(bvh_algo algo, const bvh_build_input* in, uint32_t n_tris, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_out* out, ManyLayout* lay) {
+    if (!in || !h_meshes || !out || n_meshes == 0 || !many_algo_ok(algo)) return BVH_E_INVALID_ARG;
+    if (!out->d_nodes || !out->d_prim_aabbs || !out->d_scene_extents || !out->d_roots) return BVH_E_INVALID_ARG;
+    return many_check_input(in, n_tris, h_meshes, n_meshes, lay);
+}
+// six output arrays, then the input's one or two: an output may overlap neither another output nor the input
+struct ManyRange { uintptr_t lo, hi; };
+inline ManyRange many_range(const void* p, uint64_t bytes) { return ManyRange{ (uintptr_t)p, (uintptr_t)p + (p ? bytes : 0u) }; }
+inline void many_input_ranges(const bvh_build_input* in, uint32_t n_tris, ManyRange rs[2]) {
+    const bool indexed = in->tri_format == BVH_TRI_INDEXED;
+    rs[0] = indexed ? many_range(in->d_vertices, (uint64_t)in->n_vertices * 12u) : many_range(in->d_tris, (uint64_t)n_tris * (in->tri_format == BVH_TRI_PADDED64 ? 64u : 36u));
+    rs[1] = indexed ? many_range(in->d_indices, (uint64_t)n_tris * 12u) : ManyRange{ 0, 0 };
+}
+inline bool many_overlap(const ManyRange rs[8]) {
+    for (int a = 0; a < 6; ++a)
+        for (int b = a + 1; b < 8; ++b)
+            if (rs[a].lo < rs[a].hi && rs[b].lo < rs[b].hi && rs[a].lo < rs[b].hi && rs[b].lo < rs[a].hi) return true;
+    return false;
+}
+// the output arrays of either call: LBVH (bvh_many_out: leaves NULL, mesh m's 2n-1 node records from record 2*out_off - m) or PLOC++ (bvh_many_ploc_out: roots NULL,
+// n-1 node records from record out_off - m)
+struct ManyOutAny { void* nodes; void* leaves; void* boxes; void* scenes; uint32_t* roots; uint32_t* skeys; uint32_t* svals; };
 } // namespace
 
-int bvh_build_many(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_t n_tris, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_out* out,
-                   bvh_timings* tm) {
-    if (!c) return BVH_E_INVALID_ARG;
-    ManyLayout lay;
-    int r = many_check(algo, in, n_tris, h_meshes, n_meshes, out, &lay); if (r) return r;
-    {   // the output arrays may overlap neither each other nor the input
-        struct Range { uintptr_t lo, hi; };
-        auto range = [](const void* p, uint64_t bytes) { return Range{ (uintptr_t)p, (uintptr_t)p + (p ? bytes : 0u) }; };
-        const Range rs[8] = {
-            range(out->d_nodes, (2ull * lay.total - n_meshes) * sizeof(bvh2_node)), range(out->d_prim_aabbs, lay.total * sizeof(bvh_aabb)),
-            range(out->d_scene_extents, (uint64_t)n_meshes * sizeof(bvh_aabb)), range(out->d_roots, (uint64_t)n_meshes * sizeof(u32)),
-            range(out->d_sorted_keys, lay.total * sizeof(u32)), range(out->d_sorted_vals, lay.total * sizeof(u32)),
-            in->tri_format == BVH_TRI_INDEXED ? range(in->d_vertices, (uint64_t)in->n_vertices * 12u) : range(in->d_tris, (uint64_t)n_tris * (in->tri_format == BVH_TRI_PADDED64 ? 64u : 36u)),
-            in->tri_format == BVH_TRI_INDEXED ? range(in->d_indices, (uint64_t)n_tris * 12u) : Range{ 0, 0 } };
-        for (int a = 0; a < 6; ++a)
-            for (int b = a + 1; b < 8; ++b)
-                if (rs[a].lo < rs[a].hi && rs[b].lo < rs[b].hi && rs[a].lo < rs[b].hi && rs[b].lo < rs[a].hi) return BVH_E_INVALID_ARG;
-    }
+// what bvh_build_many and bvh_build_many_ploc do once their arguments are checked
+static int many_build(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const ManyOutAny& o, const ManyLayout& lay,
+                      bvh_timings* tm) {
+    const bool ploc = algo == BVH_PLOCPP, karras = algo == BVH_LBVH_TWOPASS;
+    int r = 0;
     Bind b(c->device);
     hipStream_t s = c->stream;
     const uint32_t n_small = n_meshes - lay.n_large;
@@ -1265,7 +1272,6 @@ int bvh_build_many(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_
     const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
     const bool prof = c->profiling && sampled;
     if (prof) HIP_TRY(hipEventRecord(c->ev[5], s));
-    const bool karras = algo == BVH_LBVH_TWOPASS;
     if (n_small) {
         uint32_t at[4] = { 0u, lay.n_class[0], lay.n_class[0] + lay.n_class[1], lay.n_class[0] + lay.n_class[1] + lay.n_class[2] };
         uint32_t off = 0;
@@ -1277,11 +1283,19 @@ int bvh_build_many(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_
         HIP_TRY(hipMemcpyAsync(c->many_items, c->many_host, (size_t)n_small * sizeof(uint4), hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(c->many_ev, s));
         struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-        ManyArgs a;
-        a.tris = in->d_tris; a.verts = in->d_vertices; a.idx = in->d_indices; a.n_verts = in->n_vertices;
-        a.boxes = static_cast<bvh_aabb*>(out->d_prim_aabbs); a.scenes = static_cast<bvh_aabb*>(out->d_scene_extents); a.nodes = static_cast<bvh2_node*>(out->d_nodes);
-        a.roots = out->d_roots; a.skeys = out->d_sorted_keys; a.svals = out->d_sorted_vals;
-        launch_many(s, a, (int)in->tri_format, karras, c->many_items, lay.n_class);
+        if (ploc) {
+            ManyPlocArgs a;
+            a.tris = in->d_tris; a.verts = in->d_vertices; a.idx = in->d_indices; a.n_verts = in->n_vertices;
+            a.boxes = static_cast<bvh_aabb*>(o.boxes); a.scenes = static_cast<bvh_aabb*>(o.scenes); a.nodes = static_cast<bvh2_node*>(o.nodes);
+            a.leaves = static_cast<bvh_primref*>(o.leaves); a.skeys = o.skeys; a.svals = o.svals;
+            launch_many_ploc(s, a, (int)in->tri_format, c->many_items, lay.n_class);
+        } else {
+            ManyArgs a;
+            a.tris = in->d_tris; a.verts = in->d_vertices; a.idx = in->d_indices; a.n_verts = in->n_vertices;
+            a.boxes = static_cast<bvh_aabb*>(o.boxes); a.scenes = static_cast<bvh_aabb*>(o.scenes); a.nodes = static_cast<bvh2_node*>(o.nodes);
+            a.roots = o.roots; a.skeys = o.skeys; a.svals = o.svals;
+            launch_many(s, a, (int)in->tri_format, karras, c->many_items, lay.n_class);
+        }
         HIP_TRY(hipGetLastError());
         if (install.on) c->recorder.mark(s, nullptr);
     }
@@ -1295,13 +1309,16 @@ int bvh_build_many(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_
                 else sub.d_tris = static_cast<const char*>(in->d_tris) + (in->tri_format == BVH_TRI_PADDED64 ? 64ull : 36ull) * first;
                 bvh_result t;
                 r = build_impl(c, algo, &sub, count, &t, nullptr); if (r) return r;
-                launch_copy_bytes(s, static_cast<char*>(out->d_nodes) + (2ull * off - m) * sizeof(bvh2_node), t.d_nodes, (2ull * count - 1u) * sizeof(bvh2_node));
-                launch_copy_bytes(s, static_cast<char*>(out->d_prim_aabbs) + (uint64_t)off * sizeof(bvh_aabb), t.d_prim_aabbs, (uint64_t)count * sizeof(bvh_aabb));
-                launch_copy_bytes(s, static_cast<char*>(out->d_scene_extents) + (uint64_t)m * sizeof(bvh_aabb), t.d_scene_extent, sizeof(bvh_aabb));
-                if (out->d_sorted_keys) launch_copy_bytes(s, out->d_sorted_keys + off, t.d_sorted_keys, (uint64_t)count * sizeof(u32));
-                if (out->d_sorted_vals) launch_copy_bytes(s, out->d_sorted_vals + off, t.d_sorted_vals, (uint64_t)count * sizeof(u32));
-                if (karras) HIP_TRY(hipMemsetAsync(out->d_roots + m, 0, sizeof(u32), s));
-                else launch_copy_bytes(s, out->d_roots + m, c->small, sizeof(u32));
+                if (ploc) {
+                    launch_copy_bytes(s, static_cast<char*>(o.nodes) + ((uint64_t)off - m) * sizeof(bvh2_node), t.d_nodes, (uint64_t)(count - 1u) * sizeof(bvh2_node));
+                    launch_copy_bytes(s, static_cast<char*>(o.leaves) + (uint64_t)off * sizeof(bvh_primref), t.d_leaves, (uint64_t)count * sizeof(bvh_primref));
+                } else launch_copy_bytes(s, static_cast<char*>(o.nodes) + (2ull * off - m) * sizeof(bvh2_node), t.d_nodes, (2ull * count - 1u) * sizeof(bvh2_node));
+                launch_copy_bytes(s, static_cast<char*>(o.boxes) + (uint64_t)off * sizeof(bvh_aabb), t.d_prim_aabbs, (uint64_t)count * sizeof(bvh_aabb));
+                launch_copy_bytes(s, static_cast<char*>(o.scenes) + (uint64_t)m * sizeof(bvh_aabb), t.d_scene_extent, sizeof(bvh_aabb));
+                if (o.skeys) launch_copy_bytes(s, o.skeys + off, t.d_sorted_keys, (uint64_t)count * sizeof(u32));
+                if (o.svals) launch_copy_bytes(s, o.svals + off, t.d_sorted_vals, (uint64_t)count * sizeof(u32));
+                if (karras) HIP_TRY(hipMemsetAsync(o.roots + m, 0, sizeof(u32), s));
+                else if (!ploc) launch_copy_bytes(s, o.roots + m, c->small, sizeof(u32));
                 HIP_TRY(hipGetLastError());
             }
             off += count;
@@ -1319,6 +1336,37 @@ int bvh_build_many(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_
         }
     }
     return 0;
+}
+
+int bvh_build_many(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_t n_tris, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_out* out,
+                   bvh_timings* tm) {
+    if (!c) return BVH_E_INVALID_ARG;
+    ManyLayout lay;
+    int r = many_check(algo, in, n_tris, h_meshes, n_meshes, out, &lay); if (r) return r;
+    ManyRange rs[8] = {
+        many_range(out->d_nodes, (2ull * lay.total - n_meshes) * sizeof(bvh2_node)), many_range(out->d_prim_aabbs, lay.total * sizeof(bvh_aabb)),
+        many_range(out->d_scene_extents, (uint64_t)n_meshes * sizeof(bvh_aabb)), many_range(out->d_roots, (uint64_t)n_meshes * sizeof(u32)),
+        many_range(out->d_sorted_keys, lay.total * sizeof(u32)), many_range(out->d_sorted_vals, lay.total * sizeof(u32)) };
+    many_input_ranges(in, n_tris, rs + 6);
+    if (many_overlap(rs)) return BVH_E_INVALID_ARG;
+    const ManyOutAny o = { out->d_nodes, nullptr, out->d_prim_aabbs, out->d_scene_extents, out->d_roots, out->d_sorted_keys, out->d_sorted_vals };
+    return many_build(c, algo, in, h_meshes, n_meshes, o, lay, tm);
+}
+
+int bvh_build_many_ploc(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_t n_tris, const bvh_mesh_range* h_meshes, uint32_t n_meshes,
+                        const bvh_many_ploc_out* out, bvh_timings* tm) {
+    if (!c || !in || !h_meshes || !out || algo != BVH_PLOCPP) return BVH_E_INVALID_ARG;
+    if (!out->d_nodes || !out->d_leaves || !out->d_prim_aabbs || !out->d_scene_extents) return BVH_E_INVALID_ARG;
+    ManyLayout lay;
+    int r = many_check_input(in, n_tris, h_meshes, n_meshes, &lay); if (r) return r;
+    ManyRange rs[8] = {
+        many_range(out->d_nodes, (lay.total - n_meshes) * sizeof(bvh2_node)), many_range(out->d_leaves, lay.total * sizeof(bvh_primref)),
+        many_range(out->d_prim_aabbs, lay.total * sizeof(bvh_aabb)), many_range(out->d_scene_extents, (uint64_t)n_meshes * sizeof(bvh_aabb)),
+        many_range(out->d_sorted_keys, lay.total * sizeof(u32)), many_range(out->d_sorted_vals, lay.total * sizeof(u32)) };
+    many_input_ranges(in, n_tris, rs + 6);
+    if (many_overlap(rs)) return BVH_E_INVALID_ARG;
+    const ManyOutAny o = { out->d_nodes, out->d_leaves, out->d_prim_aabbs, out->d_scene_extents, nullptr, out->d_sorted_keys, out->d_sorted_vals };
+    return many_build(c, algo, in, h_meshes, n_meshes, o, lay, tm);
 }
 
 int bvh_many_tree(bvh_algo algo, const bvh_build_input* in, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_out* out, uint32_t m,
@@ -1340,6 +1388,34 @@ int bvh_many_tree(bvh_algo algo, const bvh_build_input* in, const bvh_mesh_range
     t.d_sorted_vals = out->d_sorted_vals ? out->d_sorted_vals + off : nullptr;
     t.root = algo == BVH_LBVH_TWOPASS ? 0u : h_roots[m];
     t.n_internal = count - 1; t.n_leaves = count; t.layout = 0; t.key_bits = 32;
+    bvh_build_input ti = *in;
+    switch (in->tri_format) {
+        case BVH_TRI_PADDED64: ti.d_tris = static_cast<const char*>(in->d_tris) + 64ull * first; t.d_tris = ti.d_tris; break;
+        case BVH_TRI_PACKED36: ti.d_tris = static_cast<const char*>(in->d_tris) + 36ull * first; break;
+        default:               ti.d_indices = static_cast<const char*>(in->d_indices) + 12ull * first; break;
+    }
+    *tree_out = t; *tris_out = ti;
+    return 0;
+}
+
+int bvh_many_ploc_tree(bvh_algo algo, const bvh_build_input* in, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_ploc_out* out, uint32_t m,
+                       bvh_result* tree_out, bvh_build_input* tris_out) {
+    if (!in || !h_meshes || !out || !tree_out || !tris_out || m >= n_meshes || algo != BVH_PLOCPP) return BVH_E_INVALID_ARG;
+    if (in->morton_bits != 30 || stage_extents_valid(in)) return BVH_E_INVALID_ARG;
+    if (!out->d_nodes || !out->d_leaves || !out->d_prim_aabbs || !out->d_scene_extents) return BVH_E_INVALID_ARG;
+    uint64_t off = 0;
+    for (uint32_t k = 0; k < m; ++k) off += h_meshes[k].count;
+    const uint32_t first = h_meshes[m].first, count = h_meshes[m].count;
+    if (count < 2 || off + count >= (1ull << 30)) return BVH_E_INVALID_ARG;
+    if (in->tri_format == BVH_TRI_PACKED36 && (first & 3u)) return BVH_E_INVALID_ARG;
+    bvh_result t; std::memset(&t, 0, sizeof t);
+    t.d_nodes = static_cast<char*>(out->d_nodes) + (off - m) * sizeof(bvh2_node);
+    t.d_leaves = static_cast<char*>(out->d_leaves) + off * sizeof(bvh_primref);
+    t.d_prim_aabbs = static_cast<char*>(out->d_prim_aabbs) + off * sizeof(bvh_aabb);
+    t.d_scene_extent = static_cast<char*>(out->d_scene_extents) + (uint64_t)m * sizeof(bvh_aabb);
+    t.d_sorted_keys = out->d_sorted_keys ? out->d_sorted_keys + off : nullptr;
+    t.d_sorted_vals = out->d_sorted_vals ? out->d_sorted_vals + off : nullptr;
+    t.root = 0u; t.n_internal = count - 1; t.n_leaves = count; t.layout = 1; t.key_bits = 32;
     bvh_build_input ti = *in;
     switch (in->tri_format) {
         case BVH_TRI_PADDED64: ti.d_tris = static_cast<const char*>(in->d_tris) + 64ull * first; t.d_tris = ti.d_tris; break;

@@ -248,6 +248,11 @@ constexpr int MANY_MAX = 512;                                // BVH_MANY_LDS_MAX
 struct ManyArgs { const void* tris; const void* verts; const void* idx; uint32_t n_verts; bvh_aabb* boxes; bvh_aabb* scenes; bvh2_node* nodes; uint32_t* roots;
                   uint32_t* skeys; uint32_t* svals; };
 void launch_many(hipStream_t s, const ManyArgs& a, int tri_format, bool karras, const void* d_items, const uint32_t n_class[4]);
+// ... and bvh_build_many_ploc's (many_ploc.hip): k_many_ploc_wave / k_many_ploc_block over the same item records; nodes = Bvh2Node[total - n_meshes] (mesh m's
+// n - 1 records from record out_off - m, root = local node 0), leaves = PrimRef[total]
+struct ManyPlocArgs { const void* tris; const void* verts; const void* idx; uint32_t n_verts; bvh_aabb* boxes; bvh_aabb* scenes; bvh2_node* nodes; bvh_primref* leaves;
+                      uint32_t* skeys; uint32_t* svals; };
+void launch_many_ploc(hipStream_t s, const ManyPlocArgs& a, int tri_format, const void* d_items, const uint32_t n_class[4]);
 
 // ---- instanced scenes (scene.hip): bvh_scene's kernels.  SceneBlas: the device copy of one validated bvh_blas (64 bytes, read whole when a ray enters an
 // instance); tris = Triangle[n] / float[9n] / the vertices of INDEXED input, idx = INDEXED indices, parent = the BLAS's k_refit_plan plan (u32[2n-1]).
@@ -295,6 +300,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

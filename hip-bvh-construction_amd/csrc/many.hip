@@ -12,7 +12,7 @@
 #include "bvh_mi355x.h"
 #include "common.hpp"
 #include "kernels.hpp"
-#include "morton.hpp"
+#include "many_front.hpp"
 
 namespace bvh {
 
@@ -29,73 +29,23 @@ template <int T> struct ManySmem {
     float red[T / WAVE][6];        // extent: one row per wave
 };
 
-// all threads of the mesh meet here: a workgroup barrier, or — one wave per mesh — nothing but ordering (a wave's LDS operations execute in order)
-template <int T> __device__ __forceinline__ void many_sync() {
-    if (T == WAVE) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else __syncthreads();
-}
-
-__device__ __forceinline__ Box wave_reduce_box_all(Box b) {           // every lane gets the union of the wave's boxes
-#pragma unroll
-    for (int m = 1; m < WAVE; m <<= 1) {
-        b.lx = fminf(b.lx, __shfl_xor(b.lx, m)); b.ly = fminf(b.ly, __shfl_xor(b.ly, m)); b.lz = fminf(b.lz, __shfl_xor(b.lz, m));
-        b.hx = fmaxf(b.hx, __shfl_xor(b.hx, m)); b.hy = fmaxf(b.hy, __shfl_xor(b.hy, m)); b.hz = fmaxf(b.hz, __shfl_xor(b.hz, m));
-    }
-    return b;
-}
-
-template <int FMT> __device__ __forceinline__ Box many_tri_box(const ManyArgs& a, u32 i) {
-    if (FMT == BVH_TRI_PADDED64) return stage_e_box_padded((const float4*)a.tris, i);
-    if (FMT == BVH_TRI_PACKED36) return stage_e_box9((const float*)a.tris + (size_t)i * 9);
-    return stage_e_box_indexed((const float*)a.verts, (const u32*)a.idx, a.n_verts, i);
-}
-
 // One mesh: triangles [it.x, it.x + it.y) of the input, output offset it.z, mesh id it.w.  t = the thread's index inside the mesh's team of T threads (T >= it.y).
 template <int T, int FMT, bool KARRAS>
 __device__ __forceinline__ void many_build_one(ManySmem<T>& sm, const ManyArgs& a, const uint4 it, const u32 t) {
-    const u32 first = it.x, n = it.y, off = it.z, m = it.w, ni = n - 1u;
+    const u32 n = it.y, off = it.z, m = it.w, ni = n - 1u;
     const bool act = t < n;
-    // 1. stage E
-    Box bx = box_empty();
+    // 1. stage E, 2. extent, 3. the mesh's bit plan, 4. the code (many_front.hpp)
+    Box bx;
+    const u64 mine = many_front<T, FMT>(a, sm.red, it, t, bx);
     if (act) {
-        bx = many_tri_box<FMT>(a, first + t);
-        box_store(a.boxes + off + t, bx);
         sm.pbox[0][t] = bx.lx; sm.pbox[1][t] = bx.ly; sm.pbox[2][t] = bx.lz; sm.pbox[3][t] = bx.hx; sm.pbox[4][t] = bx.hy; sm.pbox[5][t] = bx.hz;
-    }
-    // 2. extent: fminf / fmaxf over the mesh's boxes, starting from the reset box (k_extents' atomics give the same value in any order)
-    Box ext = wave_reduce_box_all(bx);
-    if (T > WAVE) {
-        const u32 w = t / WAVE;
-        if ((t & (WAVE - 1)) == 0) { sm.red[w][0] = ext.lx; sm.red[w][1] = ext.ly; sm.red[w][2] = ext.lz; sm.red[w][3] = ext.hx; sm.red[w][4] = ext.hy; sm.red[w][5] = ext.hz; }
-        many_sync<T>();
-        ext = box_empty();
-#pragma unroll
-        for (int k = 0; k < T / WAVE; ++k) {
-            const Box r = { sm.red[k][0], sm.red[k][1], sm.red[k][2], sm.red[k][3], sm.red[k][4], sm.red[k][5] };
-            ext = box_union(ext, r);
-        }
-    }
-    if (t == 0) box_store(a.scenes + m, ext);
-    // 3. the mesh's bit plan (every lane evaluates the same values: as cheap as one lane doing it), 4. the code
-    const float scene[6] = { ext.lx, ext.ly, ext.lz, ext.hx, ext.hy, ext.hz };
-    MortonPlan mp; float lo[3], ex[3];
-    make_plan(scene, mp, lo, ex);
-    u64 mine = 0ull;
-    if (act) {
-        const float p[3] = { ((bx.hx + bx.lx) * 0.5f - lo[0]) / ex[0], ((bx.hy + bx.ly) * 0.5f - lo[1]) / ex[1], ((bx.hz + bx.lz) * 0.5f - lo[2]) / ex[2] };   // k_morton's expression
-        const u32 code = encode(mp, p[mp.axis[0]], p[mp.axis[1]], p[mp.axis[2]]);
-        mine = ((u64)code << 32) | (u64)t;
         sm.aug[t] = mine;
     }
     sm.slot[t] = 0ull;
     many_sync<T>();
     // 5. sort: my position is the number of smaller words (every lane reads the same word: an LDS broadcast)
     if (act) {
-        u32 rank = 0u;
-        for (u32 j = 0; j < n; ++j) rank += sm.aug[j] < mine ? 1u : 0u;
+        const u32 rank = many_rank(sm.aug, n, mine);
         sm.key[rank] = (u32)(mine >> 32);
         // the leaf of position `rank` holds primitive t.  (inv[] is the position -> primitive map until the climb starts)
         if (a.skeys) a.skeys[off + rank] = (u32)(mine >> 32);

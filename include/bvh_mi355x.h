@@ -169,7 +169,7 @@ int  bvh_sort_pairs64(bvh_ctx* ctx, const uint64_t* d_keys_in, const uint32_t* d
  * (which costs ~0.1 ms of launch latency per mesh whatever its size).  Mesh m is triangles [first, first + count) of the input arrays; every mesh's arrays land
  * in a slice of six caller-owned device arrays.  out_off[m] = the sum of the counts of meshes 0 .. m-1, total = the sum of all counts (host arithmetic).
  * algo: BVH_LBVH_SINGLEPASS or BVH_LBVH_TWOPASS (two-pass: every root is 0, so a host can fill every bvh_result without a read-back); anything else is
- * BVH_E_INVALID_ARG — a batched PLOC-family emit is a later step.  in->morton_bits must be 30.
+ * BVH_E_INVALID_ARG — PLOC++ trees of a batch come from bvh_build_many_ploc below.  in->morton_bits must be 30.
  * Formats: all three.  PADDED64 / PACKED36: mesh m reads records first .. first+count of d_tris; INDEXED: index triples first .. first+count of d_indices over the
  * shared d_vertices.  Leaf primitive indices and d_sorted_vals are mesh-local, 0 .. count-1.
  * bvh_many_tree (host arithmetic only, no device work) describes mesh m's slice as a bvh_result (layout 0, key_bits 32, d_leaves / d_morton_keys NULL) plus the
@@ -205,6 +205,38 @@ int  bvh_build_many(bvh_ctx* ctx, bvh_algo algo, const bvh_build_input* in, uint
 /* host arithmetic only, no device work: mesh m's slice as a caller-filled bvh_result + the bvh_build_input that names its triangles */
 int  bvh_many_tree(bvh_algo algo, const bvh_build_input* in, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_out* out,
                    uint32_t m, const uint32_t* h_roots /* NULL allowed for BVH_LBVH_TWOPASS: root 0 */, bvh_result* tree_out, bvh_build_input* tris_out);
+
+/* ---- many small meshes in one call, PLOC++ trees ------------------------------------------------------------------------------------------
+ * bvh_build_many for trees of PLOC++ quality (bottom-level trees are built once and traced every frame): same input, ranges, out_off / total, formats (PACKED36
+ * first % 4 == 0), morton_bits 30, host-side binning (one launch per size class), item table outside the arena, asynchrony on the ctx's stream and timings
+ * (ploc_iterations stays 0) as bvh_build_many.  algo: BVH_PLOCPP only (HPLOC's parity bar is not byte identity; it is not served here).
+ * Output: PLOC layout.  Mesh m's n-1 node records start at record out_off[m] - m of d_nodes, its root is local node 0, a child >= n-1 is leaf child-(n-1); its n
+ * PrimRef leaves start at out_off[m] of d_leaves in sorted (Morton) order, prim_idx mesh-local.  bvh_many_ploc_tree (host arithmetic only) describes the slice as a
+ * bvh_result: layout 1, root 0, n_internal = count-1, key_bits 32, d_leaves set, d_morton_keys NULL; d_tris and tris_out as bvh_many_tree.
+ * Identity: for every mesh whose candidate areas are all finite — true whenever the f32 area of its extent is finite: every union of member boxes lies inside
+ * the extent and the area expression is monotone — the bytes of its node slice, leaf slice, d_prim_aabbs slice and d_sorted_keys / d_sorted_vals slices equal what
+ * bvh_build_ex(ctx2, BVH_PLOCPP, tris_out, count) produces; the extent compares equal and is byte-equal unless a coordinate is a zero of mixed sign.  The bytes depend
+ * on neither the path, nor the other meshes of the batch, nor the call.  A mesh with an infinite or NaN candidate area (boxes at +-FLT_MAX from clamped inf / NaN
+ * vertices) gets a valid tree over the same leaves in finite time — neighbour keys are compared as integers, so every round has a mutual pair — but not
+ * necessarily the ordinary build's bytes: that build's emit is compiled without NaN semantics.
+ * Paths: count <= 64: one wave per mesh, several meshes per workgroup; 65 .. BVH_MANY_LDS_MAX_PRIMS: one workgroup per mesh, all rounds in LDS, the last ones
+ * (<= 64 clusters) by its first wave; larger: bvh_build_ex(BVH_PLOCPP) on the ctx, its arrays copied to the slice — ONLY then the call counts as a build on the ctx.
+ * No kernel waits on another wave or workgroup.  Nothing but the slices is written.  bvh_ctx_kernel_times reports k_many_ploc_wave and k_many_ploc_block.
+ * Errors (BVH_E_INVALID_ARG, nothing is written or enqueued): everything bvh_build_many rejects (d_roots does not exist here), NULL d_leaves, an algo other than
+ * BVH_PLOCPP, any of the six output arrays overlapping each other or the input; bvh_many_ploc_tree: m >= n_meshes, another algo, NULL tree_out / tris_out. */
+typedef struct {
+    void*     d_nodes;          /* Bvh2Node[total - n_meshes]; mesh m's n-1 records start at record out_off[m] - m; root = local node 0 */
+    void*     d_leaves;         /* PrimRef[total] (28-byte records); mesh m's at out_off[m], in sorted (Morton) order, prim_idx mesh-local */
+    void*     d_prim_aabbs;     /* bvh_aabb[total], by mesh-local primitive index */
+    void*     d_scene_extents;  /* bvh_aabb[n_meshes] */
+    uint32_t* d_sorted_keys;    /* u32[total] or NULL */
+    uint32_t* d_sorted_vals;    /* u32[total] or NULL (mesh-local indices) */
+} bvh_many_ploc_out;
+int  bvh_build_many_ploc(bvh_ctx* ctx, bvh_algo algo /* BVH_PLOCPP */, const bvh_build_input* in, uint32_t n_tris,
+                         const bvh_mesh_range* h_meshes /* host */, uint32_t n_meshes, const bvh_many_ploc_out* out, bvh_timings* timings /* may be NULL */);
+/* host arithmetic only, no device work: mesh m's slice as a caller-filled bvh_result + the bvh_build_input that names its triangles */
+int  bvh_many_ploc_tree(bvh_algo algo, const bvh_build_input* in, const bvh_mesh_range* h_meshes, uint32_t n_meshes, const bvh_many_ploc_out* out,
+                        uint32_t m, bvh_result* tree_out, bvh_build_input* tris_out);
 
 /* ---- refit (no counterpart in the reference) ------------------------------------------------------------------------------------------
  * Recompute every box of an existing tree from new triangle positions, with the topology kept (deforming / animated meshes: vertices move, connectivity
