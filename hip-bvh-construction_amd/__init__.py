@@ -33,6 +33,7 @@ RAY = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("tmin", "<f4"), 
 HIT = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")])      # bvh_hit (bvh_intersect)
 INSTANCE = np.dtype([("object_to_world", "<f4", 12), ("blas", "<u4"), ("reserved", "<u4", 3)])                 # bvh_instance (row-major 3x4)
 INSTANCE_HIT = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4", 3)])   # bvh_instance_hit
+INSTANCE_POINT_HIT = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("instance", "<u4")])   # bvh_instance_point_hit
 POINT_QUERY = np.dtype([("point", "<f4", 3), ("radius", "<f4")])                                               # bvh_point_query (bvh_closest_point)
 POINT_HIT = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("reserved", "<u4")])   # bvh_point_hit
 KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4")])                                                         # bvh_knn_hit (bvh_knn)
@@ -40,7 +41,7 @@ KNN_MAX_K = 32
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
 TRANSFORMATION = np.dtype([("translation", "<f4", 3), ("pad", "<f4"), ("scale", "<f4", 3), ("pad1", "<f4"), ("quat", "<f4", 4), ("pad2", "<f4", 4)])
 assert RAY.itemsize == 32 and CAMERA.itemsize == 64 and TRANSFORMATION.itemsize == 64 and INSTANCE.itemsize == 64 and INSTANCE_HIT.itemsize == 32
-assert POINT_QUERY.itemsize == 16 and POINT_HIT.itemsize == 32 and KNN_HIT.itemsize == 8
+assert POINT_QUERY.itemsize == 16 and POINT_HIT.itemsize == 32 and KNN_HIT.itemsize == 8 and INSTANCE_POINT_HIT.itemsize == 32
 
 
 def qt_rotation(axis_angle):
@@ -75,7 +76,7 @@ EXPORTS = [
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
-    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas",
+    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
@@ -226,6 +227,7 @@ def lib() -> C.CDLL:
         "bvh_scene_update": ([vp, vp, i32, C.POINTER(Timings)], i32),
         "bvh_scene_intersect": ([vp, vp, u32, vp, i32], i32),
         "bvh_scene_tlas": ([vp, C.POINTER(Result)], i32),
+        "bvh_scene_closest_point": ([vp, vp, u32, vp, i32], i32),
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
@@ -1440,6 +1442,37 @@ class Scene:
         try:
             _check(lib().bvh_scene_intersect(self.handle, _ptr(rays) if rays is not None else None, n_rays, hits.ptr, q), "bvh_scene_intersect")
             return hits.download(INSTANCE_HIT, n_rays)
+        finally:
+            hits.free()
+            if own is not None:
+                own.free()
+
+    def closest_point(self, points, radius=None, query="closest", n_points: int | None = None) -> np.ndarray:
+        """bvh_scene_closest_point: ``points`` as for the builders' closest_point (a host POINT_QUERY array, a host (n, 3) float array whose radius is ``radius``
+        (None: +inf), or a device buffer of POINT_QUERY records with ``n_points``) -> host INSTANCE_POINT_HIT array, point and dist2 in world space"""
+        q = _QUERY_IDS[query] if isinstance(query, str) else int(query)
+        own = None
+        if isinstance(points, np.ndarray):
+            if points.dtype != POINT_QUERY:
+                xyz = np.asarray(points, dtype=np.float32)
+                if xyz.ndim != 2 or xyz.shape[1] != 3:
+                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
+                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
+                points["point"] = xyz
+                points["radius"] = np.float32(np.inf) if radius is None else np.float32(radius)
+            elif radius is not None:
+                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
+            n_points = points.shape[0]
+            own = points = self.ctx.upload(np.ascontiguousarray(points)) if n_points else None
+        elif n_points is None:
+            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
+            if n_points is None:
+                raise BvhError("n_points is required for device points")
+        hits = self.ctx.alloc(max(n_points, 1) * INSTANCE_POINT_HIT.itemsize)
+        self._sync_blas()
+        try:
+            _check(lib().bvh_scene_closest_point(self.handle, _ptr(points) if points is not None else None, n_points, hits.ptr, q), "bvh_scene_closest_point")
+            return hits.download(INSTANCE_POINT_HIT, n_points)
         finally:
             hits.free()
             if own is not None:

@@ -407,7 +407,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -1633,8 +1633,31 @@ int bvh_scene_intersect(bvh_scene* sc, const bvh_ray* d_rays, uint32_t n_rays, b
     SceneQuery q;
     q.rays = d_rays; q.hits = d_hits; q.overflow = sc->overflow;
     q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
-    q.n_rays = n_rays; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout;
+    q.n_rays = n_rays; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
     launch_scene_intersect(s, query, q);
+    HIP_TRY(hipGetLastError());
+    if (install.on) c->recorder.mark(s, nullptr);
+    return 0;
+}
+
+int bvh_scene_closest_point(bvh_scene* sc, const bvh_point_query* d_points, uint32_t n_points, bvh_instance_point_hit* d_hits, int query) {
+    if (!sc || !d_points || !d_hits || !sc->built) return BVH_E_INVALID_ARG;
+    if (query != BVH_QUERY_CLOSEST && query != BVH_QUERY_ANY) return BVH_E_INVALID_ARG;
+    const uintptr_t p0 = (uintptr_t)d_points, p1 = p0 + (uint64_t)n_points * sizeof(bvh_point_query), h0 = (uintptr_t)d_hits,
+                    h1 = h0 + (uint64_t)n_points * sizeof(bvh_instance_point_hit);
+    if (n_points && p0 < h1 && h0 < p1) return BVH_E_INVALID_ARG;
+    if (n_points == 0) return 0;
+    bvh_ctx* c = sc->ctx;
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    HIP_TRY(hipMemsetAsync(sc->overflow, 0, sizeof(u32), s));
+    SceneQuery q;
+    q.rays = d_points; q.hits = d_hits; q.overflow = sc->overflow;
+    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
+    q.n_rays = n_points; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
+    launch_scene_closest_point(s, query, q);
     HIP_TRY(hipGetLastError());
     if (install.on) c->recorder.mark(s, nullptr);
     return 0;

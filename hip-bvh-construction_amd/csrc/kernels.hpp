@@ -258,19 +258,24 @@ void launch_many_ploc(hipStream_t s, const ManyPlocArgs& a, int tri_format, cons
 // instance); tris = Triangle[n] / float[9n] / the vertices of INDEXED input, idx = INDEXED indices, parent = the BLAS's k_refit_plan plan (u32[2n-1]).
 struct SceneBlas { const void* nodes; const void* leaves; const void* tris; const void* idx; const uint32_t* parent; uint32_t n, root, layout, fmt, nv, pad; };
 static_assert(sizeof(SceneBlas) == 64, "SceneBlas is one 64-byte record");
-// per instance, written by k_instance_boxes: world-to-object 3x4 (row-major, f32) and the BLAS index (BVH_INVALID: inactive, never entered)
+// per instance, written by k_instance_boxes: world-to-object 3x4 (row-major, f32), the BLAS index (BVH_INVALID: inactive, never entered) and, in pad[0], the
+// bits of the f32 scale bound s2 of bvh_scene_closest_point (0 for an inactive instance)
 struct SceneInst { float w2o[12]; uint32_t blas, pad[3]; };
 static_assert(sizeof(SceneInst) == 64, "SceneInst is one 64-byte record");
 struct SceneQuery {
     const void* rays; void* hits; uint32_t* overflow;           // bvh_ray[n_rays], bvh_instance_hit[n_rays], one word zeroed before the launch
+                                                                // (point queries: bvh_point_query[n_rays], bvh_instance_point_hit[n_rays])
     const void* tnodes; const void* tleaves; const uint32_t* tparent;   // top-level tree (n_inst >= 2) and its plan
     const SceneInst* inst; const SceneBlas* blas; const void* wbox;      // SceneInst[n_inst], SceneBlas[n_blas], bvh_aabb[n_inst]
     uint32_t n_rays, n_inst, troot, tlayout;
+    const void* inst_in;                                        // bvh_instance[n_inst], the caller's records: the forward matrices (point queries only)
 };
 // one thread per instance: inverse, active flag and world box from d_instances (bvh_instance[n_inst]) and the BLASes' root boxes
 void launch_instance_boxes(hipStream_t s, const void* d_instances, uint32_t n_inst, const SceneBlas* d_blas, uint32_t n_blas, SceneInst* d_inst, void* d_wbox);
 // k_scene_intersect (short stack shared by both levels) + k_scene_intersect_deep (stackless, returns at once while *overflow == 0)
 void launch_scene_intersect(hipStream_t s, int query, const SceneQuery& q);
+// k_scene_closest_point (short stack shared by both levels) + k_scene_closest_point_deep (stackless, returns at once while *overflow == 0); scene_point.hip
+void launch_scene_closest_point(hipStream_t s, int query, const SceneQuery& q);
 
 // ---- BVH2 -> BVH4 collapse (collapse.hip)
 constexpr int COLLAPSE_MAX_BATCH = 64;                       // levels per batch of launches (one counter word per level)
@@ -300,6 +305,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

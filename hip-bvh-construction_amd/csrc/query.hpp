@@ -163,4 +163,16 @@ __device__ __forceinline__ bool ray_load(const bvh_ray* rays, u32 i, QRay& r) {
     return !nan && r.tmin < r.tmax;                               // (NaN tmin / tmax fail the comparison)
 }
 
+// ---- instanced scenes (scene.hip: bvh_scene_intersect; scene_point.hip: bvh_scene_closest_point) -----------------------------------------------------------
+constexpr u32 SCENE_BLAS_ENTRY = 0x80000000u;   // stack entry of a BLAS node (top-level entries are plain indices: n < 2^30)
+// a 3x4 row-major matrix applied to a point, in the order the header states
+__device__ __forceinline__ QF3 xf_point(const float* m, float x, float y, float z) {
+    return { ((m[0] * x + m[1] * y) + m[2] * z) + m[3], ((m[4] * x + m[5] * y) + m[6] * z) + m[7], ((m[8] * x + m[9] * y) + m[10] * z) + m[11] };
+}
+// rec_fetch with the layout chosen at run time (uniform per tree)
+__device__ __forceinline__ void rec_fetch_rt(int layout, const void* nodes, const void* leaves, u32 c, u32 ni, u32& w0, u32& w1, Box& b) {
+    if (layout == 0) rec_fetch<0>(reinterpret_cast<const bvh2_node*>(nodes), nullptr, c, ni, w0, w1, b);
+    else rec_fetch<1>(reinterpret_cast<const bvh2_node*>(nodes), reinterpret_cast<const bvh_primref*>(leaves), c, ni, w0, w1, b);
+}
+
 } // namespace bvh

@@ -10,11 +10,10 @@
 
 namespace bvh {
 
-//   k_instance_boxes       : one thread per instance: world-to-object matrix (f64 adjugate / determinant, rounded once), active flag, world box.
+//   k_instance_boxes       : one thread per instance: world-to-object matrix (f64 adjugate / determinant, rounded once), active flag, world box, scale bound s2.
 //   k_scene_intersect      : one per-lane LDS short stack shared by both levels (bit 31 of an entry marks a BLAS node); entering an instance keeps best t,
 //                            popping a top-level entry restores the world ray.  Overflow marks the ray, as k_intersect does.
 //   k_scene_intersect_deep : the marked rays, stackless: the top-level plan, and for every instance whose world box passes, that BLAS's plan.
-constexpr u32 SCENE_BLAS_ENTRY = 0x80000000u;   // stack entry of a BLAS node (top-level entries are plain indices: n < 2^30)
 constexpr int SCENE_INST_BLOCK = 256;
 
 // object_to_world M (row-major 3x4, f32) -> world_to_object, in the order the header states; false: the instance is inactive
@@ -35,8 +34,14 @@ __device__ __forceinline__ bool instance_inverse(const float* m, float* w) {
     for (int j = 0; j < 12; ++j) ok = ok && isfinite(w[j]);
     return ok;
 }
-__device__ __forceinline__ QF3 xf_point(const float* m, float x, float y, float z) {
-    return { ((m[0] * x + m[1] * y) + m[2] * z) + m[3], ((m[4] * x + m[5] * y) + m[6] * z) + m[7], ((m[8] * x + m[9] * y) + m[10] * z) + m[11] };
+// the point queries' scale bound s2 = (1 - 2^-10) / lambda of the rounded W (f32 entries as f64), lambda = max absolute row sum of W W^T >= sigma_max(W)^2
+__device__ __forceinline__ float instance_s2(const float* w) {
+    double lambda = 0.0, row[3];
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) row[j] = fabs(((double)w[4 * i] * (double)w[4 * j] + (double)w[4 * i + 1] * (double)w[4 * j + 1]) + (double)w[4 * i + 2] * (double)w[4 * j + 2]);
+        lambda = fmax(lambda, (row[0] + row[1]) + row[2]);
+    }
+    return (float)((1.0 - 0x1p-10) / lambda);
 }
 
 __global__ __launch_bounds__(SCENE_INST_BLOCK) void k_instance_boxes(const bvh_instance* __restrict__ instances, u32 n_inst, const SceneBlas* __restrict__ blas,
@@ -61,7 +66,7 @@ __global__ __launch_bounds__(SCENE_INST_BLOCK) void k_instance_boxes(const bvh_i
     }
     float4* o = reinterpret_cast<float4*>(out + k);
     o[0] = make_float4(w[0], w[1], w[2], w[3]); o[1] = make_float4(w[4], w[5], w[6], w[7]); o[2] = make_float4(w[8], w[9], w[10], w[11]);
-    o[3] = make_float4(__uint_as_float(ok ? bl : INV), 0.0f, 0.0f, 0.0f);
+    o[3] = make_float4(__uint_as_float(ok ? bl : INV), ok ? instance_s2(w) : 0.0f, 0.0f, 0.0f);
     box_store(wbox + k, wb);
 }
 
@@ -79,11 +84,6 @@ __device__ __forceinline__ bool enter_instance(const SceneQuery& a, u32 k, const
     r.nx = __float_as_uint(r.d.x) >> 31; r.ny = __float_as_uint(r.d.y) >> 31; r.nz = __float_as_uint(r.d.z) >> 31;
     r.tmin = w.tmin; r.tmax = w.tmax;
     return true;
-}
-
-__device__ __forceinline__ void rec_fetch_rt(int layout, const void* nodes, const void* leaves, u32 c, u32 ni, u32& w0, u32& w1, Box& b) {
-    if (layout == 0) rec_fetch<0>(reinterpret_cast<const bvh2_node*>(nodes), nullptr, c, ni, w0, w1, b);
-    else rec_fetch<1>(reinterpret_cast<const bvh2_node*>(nodes), reinterpret_cast<const bvh_primref*>(leaves), c, ni, w0, w1, b);
 }
 
 // leaf_test with the BLAS's format chosen at run time and the scene's order (t, instance, prim); true when an any-hit query is done

@@ -4,6 +4,7 @@
  *   Ray       32 B, alignas(32) (src/Common.h:533-539; the record bvh_generate_rays writes)      bvh_hit 16 B (bvh_intersect's output, no counterpart)
  *   bvh_instance 64 B (one placed bottom-level tree of a bvh_scene)      bvh_instance_hit 32 B (bvh_scene_intersect's output); neither has a counterpart
  *   bvh_point_query 16 B (bvh_closest_point's input)      bvh_point_hit 32 B (its output); neither has a counterpart
+ *   bvh_instance_point_hit 32 B (bvh_scene_closest_point's output: bvh_point_hit with the instance in its last word); no counterpart
  *   bvh_knn_hit 8 B (one entry of bvh_knn's lists and one record of bvh_radius_search's slices; both read bvh_point_query too); no counterpart
  * Usable from C, C++ and HIP device code. */
 #ifndef BVH_TYPES_H
@@ -37,6 +38,8 @@ typedef struct { float dist2; uint32_t prim_idx; } bvh_knn_hit;
 /* object_to_world: row-major 3x4 matrix {m00 m01 m02 m03, m10 .. m13, m20 .. m23}; world = M * (object, 1).  blas: index into the scene's bottom-level table */
 typedef struct { float object_to_world[12]; uint32_t blas; uint32_t reserved[3]; } bvh_instance;
 typedef struct { float t, u, v; uint32_t prim_idx, instance_idx; uint32_t reserved[3]; } bvh_instance_hit;
+/* point: the closest point of instance instance_idx's triangle prim_idx in WORLD space, dist2 = its squared world distance, (u, v) = the weights of v2 and v3 */
+typedef struct { bvh_float3 point; float dist2; float u, v; uint32_t prim_idx, instance_idx; } bvh_instance_point_hit;
 
 #ifdef __cplusplus
 static_assert(sizeof(bvh_aabb) == 24, "Aabb is 24 bytes");
@@ -50,6 +53,7 @@ static_assert(sizeof(bvh_point_hit) == 32, "bvh_point_hit is 32 bytes");
 static_assert(sizeof(bvh_knn_hit) == 8, "bvh_knn_hit is 8 bytes");
 static_assert(sizeof(bvh_instance) == 64, "bvh_instance is 64 bytes");
 static_assert(sizeof(bvh_instance_hit) == 32, "bvh_instance_hit is 32 bytes");
+static_assert(sizeof(bvh_instance_point_hit) == 32, "bvh_instance_point_hit is 32 bytes");
 #endif
 
 #endif

@@ -625,7 +625,29 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  * after validation leaves the scene unbuilt (queries and updates then return BVH_E_INVALID_ARG until a build succeeds).  timings: the top-level build's
  * (bvh_build_boxes; all zero with one instance).  Blocking (the descriptors are copied from host memory before any kernel is enqueued).
  * bvh_scene_tlas: the top-level tree as a bvh_result — layout by algo, d_prim_aabbs = the world boxes by instance index, d_tris / d_scene_extent / d_sorted_* /
- * d_morton_keys NULL — readable by bvh_sah_cost, bvh_checksum and bvh_download (nodes and leaves).  Valid until the next bvh_scene_build or bvh_scene_destroy. */
+ * d_morton_keys NULL — readable by bvh_sah_cost, bvh_checksum and bvh_download (nodes and leaves).  Valid until the next bvh_scene_build or bvh_scene_destroy.
+ * Point queries: bvh_scene_closest_point answers d_points[i] (bvh_point_query, as bvh_closest_point reads it) with d_hits[i]: the nearest surface point over
+ * all active instances, in world space.  Everything is f32 with no contraction in the stated order (tests/test_scene_point.py restates it in numpy).
+ *   candidate of (instance k, primitive j): the world triangle V_i = M_k v_i, V_i.r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3 (the order of the world box), and
+ *     bvh_closest_point's formula tri_closest(V1, V2, V3, p) word for word: point and dist2 are world-space values that do not depend on how the tree is walked.
+ *     Accepted iff dist2 <= r2 = radius * radius (NaN never; an infinite radius is no bound).  Queries with a NaN coordinate, a NaN radius or radius < 0 miss.
+ *     Inactive instances never answer.
+ *   BVH_QUERY_CLOSEST: the accepted candidate with the smallest (dist2, instance_idx, prim_idx), compared lexicographically.  BVH_QUERY_ANY: some accepted
+ *     candidate (the walk stops at the first).  Hit = {point, dist2, u, v, prim_idx, instance_idx}; miss = {0, 0, 0, r2, 0, 0, BVH_INVALID, BVH_INVALID}.
+ *   scale bound s2 of an instance (0 if inactive; recomputed by bvh_scene_update): from the rounded f32 world_to_object entries w_ij taken as f64,
+ *     S_ij = (w_i0 w_j0 + w_i1 w_j1) + w_i2 w_j2, lambda = max_i (|S_i0| + |S_i1|) + |S_i2|, s2 = (float)((1 - 2^-10) / lambda).  lambda >= sigma_max(W)^2
+ *     (Gershgorin), so |M x - p|^2 >= s2 |x - W p|^2 for every object point x: tight for rotation x uniform scale, within 3x otherwise.
+ *   box tests.  Top level: bvh_closest_point's (box_dist_pass) on the instances' world boxes with the world point.  Inside instance k: the point
+ *     p' = W_k p in the order of o' above, the slack e = 2^-20 max_i(((|w_i0||px| + |w_i1||py|) + |w_i2||pz|) + |w_i3|); a node box grows on every axis by
+ *     2^-16 * (its largest |coordinate|) + e, lb' is its f32 squared distance to p' as in box_dist_pass, and the subtree is culled iff
+ *     s2 * lb' * (1 - 2^-20) > best (a NaN product never culls), best being the world-space dist2 so far (r2 at the start), carried across instances.
+ *   well-conditioned (answers exact): for the true answer (k, j), (1) with p* = W_k p in f64 from the stored f32 entries, s2_k times the f64
+ *     squared distance from p* to triangle j's object box grown by 2^-17 * (its largest |coordinate|) + e / 2 is <= the answer's dist2, and (2) the f64 squared
+ *     distance from p to instance k's world box grown by 2^-17 * (its largest |coordinate|) is <= that dist2.  On every query a reported hit is an accepted
+ *     candidate of its (instance, prim) with bit-equal point, dist2, u, v, and a closest answer is never lexicographically below the true one.
+ * Asynchronous on the ctx's stream, no read-back; no depth limit at either level.  bvh_ctx_kernel_times reports k_scene_closest_point and
+ * k_scene_closest_point_deep.  Errors write and enqueue nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene, NULL d_points or d_hits, a query other than 0 or 1,
+ * overlapping d_points / d_hits ranges.  n_points == 0 returns 0 and touches nothing.  BLAS ordering as for bvh_scene_intersect. */
 typedef struct { bvh_result tree; bvh_build_input tris; } bvh_blas;   /* tris.tri_format PADDED64 with d_tris NULL: tree.d_tris is Triangle[n_leaves] */
 typedef struct bvh_scene bvh_scene;
 int  bvh_scene_create(bvh_ctx* ctx, bvh_scene** out);
@@ -634,6 +656,7 @@ int  bvh_scene_build(bvh_scene* scene, bvh_algo algo, const bvh_blas* blas /* ho
                      const bvh_instance* instances, uint32_t n_instances, int instances_on_device, bvh_timings* timings /* may be NULL */);
 int  bvh_scene_update(bvh_scene* scene, const bvh_instance* instances, int instances_on_device, bvh_timings* timings /* may be NULL */);
 int  bvh_scene_intersect(bvh_scene* scene, const bvh_ray* d_rays, uint32_t n_rays, bvh_instance_hit* d_hits, int query /* bvh_query_kind */);
+int  bvh_scene_closest_point(bvh_scene* scene, const bvh_point_query* d_points, uint32_t n_points, bvh_instance_point_hit* d_hits, int query /* bvh_query_kind */);
 int  bvh_scene_tlas(const bvh_scene* scene, bvh_result* out);
 
 /* ---- stage-level entry points (one per reference kernel / library call on the path) -------------------------- */
