@@ -76,7 +76,7 @@ EXPORTS = [
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
-    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point",
+    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
@@ -228,6 +228,7 @@ def lib() -> C.CDLL:
         "bvh_scene_intersect": ([vp, vp, u32, vp, i32], i32),
         "bvh_scene_tlas": ([vp, C.POINTER(Result)], i32),
         "bvh_scene_closest_point": ([vp, vp, u32, vp, i32], i32),
+        "bvh_scene_intersect_all": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
@@ -1475,6 +1476,55 @@ class Scene:
             return hits.download(INSTANCE_POINT_HIT, n_points)
         finally:
             hits.free()
+            if own is not None:
+                own.free()
+
+    def intersect_all(self, rays, sorted: bool = True, count_only: bool = False, capacity: int | None = None, n_rays: int | None = None):
+        """bvh_scene_intersect_all: every accepted hit along each ray over all active instances.  ``rays`` a host RAY array or a device buffer (DeviceBuffer /
+        int address, with ``n_rays``).  Returns host arrays (offsets u32[n + 1], hits INSTANCE_HIT[total]): ray i's hits are hits[offsets[i]:offsets[i + 1]],
+        in ascending (t, instance, prim) order when ``sorted`` (BVH_HITS_SORTED), in no particular order otherwise; an empty slice is a miss.  ``count_only``
+        returns offsets alone.  ``capacity`` None: a count-only call first, then a call with the exact capacity; a given capacity that is too small is
+        re-allocated with the total the call reported and the call repeated once."""
+        ctx = self.ctx
+        own = None
+        if isinstance(rays, np.ndarray):
+            if rays.dtype != RAY:
+                raise BvhError("rays must have dtype RAY (32-byte records)")
+            n_rays = rays.shape[0]
+            own = rays = ctx.upload(np.ascontiguousarray(rays)) if n_rays else None
+        elif n_rays is None:
+            n_rays = rays.nbytes // RAY.itemsize if isinstance(rays, DeviceBuffer) else None
+            if n_rays is None:
+                raise BvhError("n_rays is required for device rays")
+        if n_rays == 0:                                   # no rays: the empty answer, without a call
+            off = np.zeros(1, dtype=np.uint32)
+            return off if count_only else (off, np.zeros(0, dtype=INSTANCE_HIT))
+        flags = HITS_SORTED if sorted else 0
+        what = "bvh_scene_intersect_all"
+        offsets = ctx.alloc((n_rays + 1) * 4)
+        hits = None
+        self._sync_blas()
+        try:
+            total = C.c_uint64()
+            if count_only or capacity is None:
+                _check(lib().bvh_scene_intersect_all(self.handle, _ptr(rays), n_rays, flags, offsets.ptr, None, 0, C.byref(total)), what)
+                if count_only:
+                    return offsets.download(np.uint32, n_rays + 1)
+                cap = total.value
+            else:
+                cap = int(capacity)
+            for _ in range(2):
+                hits = ctx.alloc(max(cap, 1) * INSTANCE_HIT.itemsize)
+                _check(lib().bvh_scene_intersect_all(self.handle, _ptr(rays), n_rays, flags, offsets.ptr, hits.ptr, cap, C.byref(total)), what)
+                if total.value <= cap:
+                    break
+                hits.free(); hits = None
+                cap = total.value
+            return offsets.download(np.uint32, n_rays + 1), hits.download(INSTANCE_HIT, total.value)
+        finally:
+            offsets.free()
+            if hits is not None:
+                hits.free()
             if own is not None:
                 own.free()
 

@@ -276,6 +276,15 @@ void launch_instance_boxes(hipStream_t s, const void* d_instances, uint32_t n_in
 void launch_scene_intersect(hipStream_t s, int query, const SceneQuery& q);
 // k_scene_closest_point (short stack shared by both levels) + k_scene_closest_point_deep (stackless, returns at once while *overflow == 0); scene_point.hip
 void launch_scene_closest_point(hipStream_t s, int query, const SceneQuery& q);
+// bvh_scene_intersect_all's extra arguments (scene_multihit.hip), beside a SceneQuery whose hits field is unused and whose overflow word is the pass's own:
+// offsets = u32[n_rays + 1] (the count pass's counts, then the scan's offsets), hits = bvh_instance_hit[capacity] (fill pass), total = the scan's 64-bit total
+struct SceneHits { uint32_t* offsets; void* hits; const uint64_t* total; uint64_t capacity; };
+// k_scene_hits_count (short stack shared by both levels; offsets[i] = ray i's number of accepted hits) + k_scene_hits_deep (stackless, returns at once while
+// *q.overflow == 0) + launch_overlap_scan.  launch_scene_hits_fill: k_scene_hits_fill + k_scene_hits_deep, which return at once unless *h.total <= h.capacity
+// and *h.total < 2^32; ray i's records go to hits[offsets[i] ..], in ascending (t, instance, prim) order when sorted != 0.  Each pass has an overflow word of
+// its own, zeroed before the launches
+void launch_scene_hits_count(hipStream_t s, const SceneQuery& q, const SceneHits& h, uint64_t* d_sums, uint64_t* d_total);
+void launch_scene_hits_fill(hipStream_t s, int sorted, const SceneQuery& q, const SceneHits& h);
 
 // ---- BVH2 -> BVH4 collapse (collapse.hip)
 constexpr int COLLAPSE_MAX_BATCH = 64;                       // levels per batch of launches (one counter word per level)
@@ -305,6 +314,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_multihit(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

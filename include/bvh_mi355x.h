@@ -647,7 +647,36 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  *     candidate of its (instance, prim) with bit-equal point, dist2, u, v, and a closest answer is never lexicographically below the true one.
  * Asynchronous on the ctx's stream, no read-back; no depth limit at either level.  bvh_ctx_kernel_times reports k_scene_closest_point and
  * k_scene_closest_point_deep.  Errors write and enqueue nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene, NULL d_points or d_hits, a query other than 0 or 1,
- * overlapping d_points / d_hits ranges.  n_points == 0 returns 0 and touches nothing.  BLAS ordering as for bvh_scene_intersect. */
+ * overlapping d_points / d_hits ranges.  n_points == 0 returns 0 and touches nothing.  BLAS ordering as for bvh_scene_intersect.
+ * All hits: bvh_scene_intersect_all is bvh_intersect_all on a scene — which triangles of which instances does each ray cross, ALL of them?  Its contract is the
+ * union of bvh_scene_intersect's and bvh_intersect_all's; nothing in it is new arithmetic.
+ *   hit test and acceptance: bvh_scene_intersect's, word for word — tri_hit on the object-space ray made by the instance maths above, accepted iff
+ *     iu > 0 && iv > 0 && iw > 0 && tmin < it < tmax; t is not rescaled.  Inactive instances never answer.  A ray with a NaN component, or with
+ *     !(tmin < tmax), accepts nothing.
+ *   answer: ray i's set is ALL its accepted hits over all active instances, in compressed-row form: d_hits[d_offsets[i] .. d_offsets[i+1]) is ray i's slice,
+ *     d_offsets[0] = 0, d_offsets[n_rays] = the total.  A record is {it, iu, iv, prim_idx, instance_idx, 0, 0, 0}.  Each (instance, prim) pair appears at most
+ *     once per slice.  There are no miss records: an empty slice is a miss.  With d_hits == NULL the call only counts.
+ *   order inside a slice: without BVH_HITS_SORTED unspecified, but the same call on the same arrays gives the same bytes.  With BVH_HITS_SORTED each slice is
+ *     ascending in (t, instance_idx, prim_idx), compared lexicographically — the scene's closest-hit order, so a slice's first record is the BVH_QUERY_CLOSEST
+ *     answer; the whole d_hits array then depends on none of the top-level builder, the BLAS builders, the layouts, the formats, the traversal order.
+ *   box tests: bvh_intersect's conservative test at both levels, against [tmin, tmax] for the whole walk: the bound never shrinks.
+ *   well-conditioned: bvh_scene_intersect's definition applied to EVERY accepted hit of the ray — the object-space ray is well-conditioned for its BLAS for
+ *     that hit (§8b), and the hit's world point o + t d (f64) lies in its instance's world box grown by half the box test's growth.  On such rays the set is
+ *     exact.  On EVERY ray each record is an accepted hit of its (instance, prim) with bit-equal t / u / v, and the slice is a subset of the true set.
+ *   passes, capacity, total_out, saturation, asynchrony: exactly bvh_intersect_all's.  The call always counts and scans; the fill decides ON THE DEVICE whether
+ *     it runs (d_hits != NULL, total <= capacity and total < 2^32); a skipped fill leaves d_hits untouched and d_offsets complete; total_out != NULL is the
+ *     only host wait (an 8-byte read-back); a total of 2^32 or more saturates d_offsets at 0xFFFFFFFF and returns BVH_E_TOO_LARGE when total_out was given
+ *     (with *total_out set); d_hits is never written outside ray i's slice nor past the total.  The scratch words are the ctx's, as for bvh_intersect_all; on
+ *     a ctx that has no arena yet (a one-instance scene on a fresh ctx) the first call reserves the smallest one, as bvh_ctx_reserve(ctx, 2) would.
+ *   per-ray counter: a scene ray's count is not bounded by 2^30 (it can cross many instances of one BLAS), so the per-ray counter saturates at 0xFFFFFFFD
+ *     (one below the internal mark 0xFFFFFFFE of a ray left to the stackless pass): the mark is never a count.
+ *   no depth limit at either level: a ray whose short stack would overflow is finished by a stackless pass through the plans the scene owns.  Both passes
+ *     test the same boxes (every record below a root; neither the top-level root's own box nor a BLAS root's, for which the instance's world box stands), so
+ *     count and fill agree on every ray's set whichever pass served it.
+ *   errors enqueue and write nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene; NULL d_rays or d_offsets; a flag bit other than BVH_HITS_SORTED;
+ *     n_rays >= 2^30; d_offsets or d_hits (capacity records, clamped to 2^32 - 1) overlapping d_rays or each other.
+ *   n_rays == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
+ *   bvh_ctx_kernel_times reports k_scene_hits_count, k_scene_hits_fill, k_scene_hits_deep (after each pass) and k_overlap_scan. */
 typedef struct { bvh_result tree; bvh_build_input tris; } bvh_blas;   /* tris.tri_format PADDED64 with d_tris NULL: tree.d_tris is Triangle[n_leaves] */
 typedef struct bvh_scene bvh_scene;
 int  bvh_scene_create(bvh_ctx* ctx, bvh_scene** out);
@@ -657,6 +686,9 @@ int  bvh_scene_build(bvh_scene* scene, bvh_algo algo, const bvh_blas* blas /* ho
 int  bvh_scene_update(bvh_scene* scene, const bvh_instance* instances, int instances_on_device, bvh_timings* timings /* may be NULL */);
 int  bvh_scene_intersect(bvh_scene* scene, const bvh_ray* d_rays, uint32_t n_rays, bvh_instance_hit* d_hits, int query /* bvh_query_kind */);
 int  bvh_scene_closest_point(bvh_scene* scene, const bvh_point_query* d_points, uint32_t n_points, bvh_instance_point_hit* d_hits, int query /* bvh_query_kind */);
+int  bvh_scene_intersect_all(bvh_scene* scene, const bvh_ray* d_rays, uint32_t n_rays, uint32_t flags /* 0 or BVH_HITS_SORTED */,
+                             uint32_t* d_offsets /* u32[n_rays + 1], device */, bvh_instance_hit* d_hits /* [capacity], device, or NULL: count only */,
+                             uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
 int  bvh_scene_tlas(const bvh_scene* scene, bvh_result* out);
 
 /* ---- stage-level entry points (one per reference kernel / library call on the path) -------------------------- */
