@@ -38,10 +38,12 @@ POINT_QUERY = np.dtype([("point", "<f4", 3), ("radius", "<f4")])                
 POINT_HIT = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("reserved", "<u4")])   # bvh_point_hit
 KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4")])                                                         # bvh_knn_hit (bvh_knn)
 KNN_MAX_K = 32
+INSTANCE_KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4")])         # bvh_instance_knn_hit (bvh_scene_knn)
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
 TRANSFORMATION = np.dtype([("translation", "<f4", 3), ("pad", "<f4"), ("scale", "<f4", 3), ("pad1", "<f4"), ("quat", "<f4", 4), ("pad2", "<f4", 4)])
 assert RAY.itemsize == 32 and CAMERA.itemsize == 64 and TRANSFORMATION.itemsize == 64 and INSTANCE.itemsize == 64 and INSTANCE_HIT.itemsize == 32
 assert POINT_QUERY.itemsize == 16 and POINT_HIT.itemsize == 32 and KNN_HIT.itemsize == 8 and INSTANCE_POINT_HIT.itemsize == 32
+assert INSTANCE_KNN_HIT.itemsize == 16
 
 
 def qt_rotation(axis_angle):
@@ -76,7 +78,7 @@ EXPORTS = [
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
-    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all",
+    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
@@ -228,6 +230,7 @@ def lib() -> C.CDLL:
         "bvh_scene_intersect": ([vp, vp, u32, vp, i32], i32),
         "bvh_scene_tlas": ([vp, C.POINTER(Result)], i32),
         "bvh_scene_closest_point": ([vp, vp, u32, vp, i32], i32),
+        "bvh_scene_knn": ([vp, vp, u32, u32, vp, vp], i32),
         "bvh_scene_intersect_all": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
@@ -1476,6 +1479,42 @@ class Scene:
             return hits.download(INSTANCE_POINT_HIT, n_points)
         finally:
             hits.free()
+            if own is not None:
+                own.free()
+
+    def knn(self, points, k: int, radius=None, n_points: int | None = None):
+        """bvh_scene_knn: the ``k`` (1 .. KNN_MAX_K) nearest triangles within each query's radius over all active instances.  ``points`` as for closest_point
+        (a host POINT_QUERY array, a host (n, 3) float array whose radius is ``radius`` (None: +inf), or a device buffer of POINT_QUERY records with
+        ``n_points``).  Returns host arrays (hits INSTANCE_KNN_HIT[n, k], counts u32[n]): hits[i, :counts[i]] is query i's list in ascending
+        (dist2, instance, prim) order, dist2 in world space; the slots past it are {radius * radius, INVALID, INVALID, 0}."""
+        k = int(k)
+        if not 1 <= k <= KNN_MAX_K:
+            raise BvhError(f"k must be 1 .. {KNN_MAX_K}")
+        own = None
+        if isinstance(points, np.ndarray):
+            if points.dtype != POINT_QUERY:
+                xyz = np.asarray(points, dtype=np.float32)
+                if xyz.ndim != 2 or xyz.shape[1] != 3:
+                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
+                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
+                points["point"] = xyz
+                points["radius"] = np.float32(np.inf) if radius is None else np.float32(radius)
+            elif radius is not None:
+                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
+            n_points = points.shape[0]
+            own = points = self.ctx.upload(np.ascontiguousarray(points)) if n_points else None
+        elif n_points is None:
+            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
+            if n_points is None:
+                raise BvhError("n_points is required for device points")
+        hits = self.ctx.alloc(max(n_points * k, 1) * INSTANCE_KNN_HIT.itemsize)
+        counts = self.ctx.alloc(max(n_points, 1) * 4)
+        self._sync_blas()
+        try:
+            _check(lib().bvh_scene_knn(self.handle, _ptr(points) if points is not None else None, n_points, k, hits.ptr, counts.ptr), "bvh_scene_knn")
+            return hits.download(INSTANCE_KNN_HIT, n_points * k).reshape(n_points, k), counts.download(np.uint32, n_points)
+        finally:
+            hits.free(); counts.free()
             if own is not None:
                 own.free()
 

@@ -407,7 +407,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_multihit(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -1658,6 +1658,38 @@ int bvh_scene_closest_point(bvh_scene* sc, const bvh_point_query* d_points, uint
     q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
     q.n_rays = n_points; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
     launch_scene_closest_point(s, query, q);
+    HIP_TRY(hipGetLastError());
+    if (install.on) c->recorder.mark(s, nullptr);
+    return 0;
+}
+
+// bvh_scene_closest_point's scene and bvh_knn's argument rules; every argument is checked before anything is enqueued, so an error writes nothing
+int bvh_scene_knn(bvh_scene* sc, const bvh_point_query* d_points, uint32_t n_points, uint32_t k, bvh_instance_knn_hit* d_hits, uint32_t* d_counts) {
+    if (!sc || !d_points || !d_hits || !sc->built) return BVH_E_INVALID_ARG;
+    if (k == 0u || k > (uint32_t)BVH_KNN_MAX_K) return BVH_E_INVALID_ARG;
+    if ((uint64_t)n_points * k >= (1ull << 32)) return BVH_E_INVALID_ARG;
+    if (n_points) {                                           // the three caller arrays must not overlap
+        const uint64_t p_bytes = (uint64_t)n_points * sizeof(bvh_point_query), h_bytes = (uint64_t)n_points * k * sizeof(bvh_instance_knn_hit);
+        const uintptr_t p0 = (uintptr_t)d_points, p1 = p0 + p_bytes, h0 = (uintptr_t)d_hits, h1 = h0 + h_bytes;
+        if (p0 < h1 && h0 < p1) return BVH_E_INVALID_ARG;
+        if (d_counts) {
+            const uintptr_t c0 = (uintptr_t)d_counts, c1 = c0 + (uint64_t)n_points * sizeof(u32);
+            if ((c0 < p1 && p0 < c1) || (c0 < h1 && h0 < c1)) return BVH_E_INVALID_ARG;
+        }
+    }
+    if (n_points == 0) return 0;
+    bvh_ctx* c = sc->ctx;
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    HIP_TRY(hipMemsetAsync(sc->overflow, 0, sizeof(u32), s));
+    SceneQuery q;
+    q.rays = d_points; q.hits = d_hits; q.overflow = sc->overflow;
+    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
+    q.n_rays = n_points; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
+    q.counts = d_counts; q.k = k;
+    launch_scene_knn(s, q);
     HIP_TRY(hipGetLastError());
     if (install.on) c->recorder.mark(s, nullptr);
     return 0;

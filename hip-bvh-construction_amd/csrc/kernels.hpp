@@ -269,6 +269,8 @@ struct SceneQuery {
     const SceneInst* inst; const SceneBlas* blas; const void* wbox;      // SceneInst[n_inst], SceneBlas[n_blas], bvh_aabb[n_inst]
     uint32_t n_rays, n_inst, troot, tlayout;
     const void* inst_in;                                        // bvh_instance[n_inst], the caller's records: the forward matrices (point queries only)
+    uint32_t* counts = nullptr; uint32_t k = 0, pad = 0;        // bvh_scene_knn only (appended: the other kernels never read them): hits =
+                                                                // bvh_instance_knn_hit[n_rays * k], counts = u32[n_rays] or null, 1 <= k <= KNN_MAX_K
 };
 // one thread per instance: inverse, active flag and world box from d_instances (bvh_instance[n_inst]) and the BLASes' root boxes
 void launch_instance_boxes(hipStream_t s, const void* d_instances, uint32_t n_inst, const SceneBlas* d_blas, uint32_t n_blas, SceneInst* d_inst, void* d_wbox);
@@ -276,6 +278,9 @@ void launch_instance_boxes(hipStream_t s, const void* d_instances, uint32_t n_in
 void launch_scene_intersect(hipStream_t s, int query, const SceneQuery& q);
 // k_scene_closest_point (short stack shared by both levels) + k_scene_closest_point_deep (stackless, returns at once while *overflow == 0); scene_point.hip
 void launch_scene_closest_point(hipStream_t s, int query, const SceneQuery& q);
+// k_scene_knn<8 / 16 / 32 by q.k> (k_scene_closest_point's walk, the list in LDS beside the stack; marks a query it leaves in hits[i * k].prim_idx) +
+// k_scene_knn_deep (stackless, returns at once while *overflow == 0); scene_knn.hip
+void launch_scene_knn(hipStream_t s, const SceneQuery& q);
 // bvh_scene_intersect_all's extra arguments (scene_multihit.hip), beside a SceneQuery whose hits field is unused and whose overflow word is the pass's own:
 // offsets = u32[n_rays + 1] (the count pass's counts, then the scan's offsets), hits = bvh_instance_hit[capacity] (fill pass), total = the scan's 64-bit total
 struct SceneHits { uint32_t* offsets; void* hits; const uint64_t* total; uint64_t capacity; };
@@ -314,6 +319,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_multihit(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

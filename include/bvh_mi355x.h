@@ -648,6 +648,29 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  * Asynchronous on the ctx's stream, no read-back; no depth limit at either level.  bvh_ctx_kernel_times reports k_scene_closest_point and
  * k_scene_closest_point_deep.  Errors write and enqueue nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene, NULL d_points or d_hits, a query other than 0 or 1,
  * overlapping d_points / d_hits ranges.  n_points == 0 returns 0 and touches nothing.  BLAS ordering as for bvh_scene_intersect.
+ * k nearest: bvh_scene_knn is bvh_knn on a scene — the k nearest triangles of each point within its radius, over all active instances.  Its contract is the
+ * union of bvh_scene_closest_point's and bvh_knn's; nothing in it is new arithmetic (tests/test_scene_knn.py restates it in numpy).
+ *   candidate and acceptance: bvh_scene_closest_point's, word for word — the world triangle V_i = M_k v_i in the stated order, dist2 = tri_closest(V1, V2, V3, p),
+ *     accepted iff dist2 <= r2 = radius * radius in f32.  A query with a NaN coordinate, a NaN radius or radius < 0 accepts nothing.  Inactive instances never
+ *     answer; a triangle with a NaN world vertex is never accepted.
+ *   answer: query i's list, d_hits[i*k .. i*k+k), is the min(k, accepted) accepted candidates with the smallest (dist2, instance_idx, prim_idx), compared
+ *     lexicographically and stored in ascending order as {dist2, prim_idx, instance_idx, 0} records; each (instance, prim) pair appears at most once.  The list
+ *     depends on none of the top-level builder, the BLAS builders, the layouts, the formats, the traversal order.  Slots past the list are
+ *     {r2, BVH_INVALID, BVH_INVALID, 0}: all k of them for a query that accepts nothing.  d_counts[i], when given, is the list's length.  1 <= k <= BVH_KNN_MAX_K.
+ *   relation to the other queries: with k == 1, (dist2, prim_idx, instance_idx) are bvh_scene_closest_point's BVH_QUERY_CLOSEST fields bit for bit, on every
+ *     query (the walk is the same: near child first by lower bound at both levels, equal bounds go left).  With one identity instance, (dist2, prim_idx) are
+ *     bvh_knn's on the BLAS, on well-conditioned queries.
+ *   box tests: bvh_scene_closest_point's, unchanged — box_dist_pass on the world boxes at the top level; inside instance k the mapped point p' = W_k p, the
+ *     slack e, boxes grown by 2^-16 * (their largest |coordinate|) + e, a subtree culled iff s2 * lb' * (1 - 2^-20) > bound (a NaN product never culls).  bound
+ *     is the dist2 of the list's last entry once the list holds k entries and r2 before that; it is carried across instances and level changes.
+ *   well-conditioned (lists exact): every entry of the query's true list meets bvh_scene_closest_point's conditions (1) and (2) against that
+ *     entry's own dist2.  The bound never drops below the true k-th dist2, so no ancestor of a true entry is culled at either level.  On EVERY query each
+ *     reported entry is an accepted candidate of its (instance, prim) with bit-equal dist2, the entries strictly ascend, and no list is lexicographically
+ *     below the true one.
+ *   no depth limit at either level: a query whose push would overflow the short stack, or whose walk exceeds the node count, is finished by a stackless pass
+ *     through the plans the scene owns.  Asynchronous on the ctx's stream, no read-back.  bvh_ctx_kernel_times reports k_scene_knn and k_scene_knn_deep.
+ *   errors write and enqueue nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene; NULL d_points or d_hits; k == 0 or k > BVH_KNN_MAX_K; n_points * k >= 2^32;
+ *     the d_points / d_hits / d_counts ranges overlapping each other.  n_points == 0 returns 0 and touches nothing.  BLAS ordering as for bvh_scene_intersect.
  * All hits: bvh_scene_intersect_all is bvh_intersect_all on a scene — which triangles of which instances does each ray cross, ALL of them?  Its contract is the
  * union of bvh_scene_intersect's and bvh_intersect_all's; nothing in it is new arithmetic.
  *   hit test and acceptance: bvh_scene_intersect's, word for word — tri_hit on the object-space ray made by the instance maths above, accepted iff
@@ -686,6 +709,8 @@ int  bvh_scene_build(bvh_scene* scene, bvh_algo algo, const bvh_blas* blas /* ho
 int  bvh_scene_update(bvh_scene* scene, const bvh_instance* instances, int instances_on_device, bvh_timings* timings /* may be NULL */);
 int  bvh_scene_intersect(bvh_scene* scene, const bvh_ray* d_rays, uint32_t n_rays, bvh_instance_hit* d_hits, int query /* bvh_query_kind */);
 int  bvh_scene_closest_point(bvh_scene* scene, const bvh_point_query* d_points, uint32_t n_points, bvh_instance_point_hit* d_hits, int query /* bvh_query_kind */);
+int  bvh_scene_knn(bvh_scene* scene, const bvh_point_query* d_points, uint32_t n_points, uint32_t k,
+                   bvh_instance_knn_hit* d_hits /* [n_points * k], query i's list at d_hits[i*k .. i*k+k) */, uint32_t* d_counts /* [n_points] or NULL */);
 int  bvh_scene_intersect_all(bvh_scene* scene, const bvh_ray* d_rays, uint32_t n_rays, uint32_t flags /* 0 or BVH_HITS_SORTED */,
                              uint32_t* d_offsets /* u32[n_rays + 1], device */, bvh_instance_hit* d_hits /* [capacity], device, or NULL: count only */,
                              uint64_t capacity, uint64_t* total_out /* host, may be NULL */);

@@ -14,6 +14,7 @@ for f in lbvh collapse; do /opt/rocm/bin/hipcc $FLAGS -fno-honor-nans -mno-amdgp
 for f in hploc ploc; do /opt/rocm/bin/hipcc $FLAGS -fno-honor-nans -mno-amdgpu-ieee ${NOSLP--fno-slp-vectorize} $EXTRA -c $f.hip -o $OBJ/$f.o & done     # (as the Makefile; NOSLP="" builds them with the SLP vectoriser)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene.hip -o $OBJ/scene.o &     # (as the Makefile: never with the SLP vectoriser, scene.hip says why)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene_point.hip -o $OBJ/scene_point.o &     # (as the Makefile)
+/opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene_knn.hip -o $OBJ/scene_knn.o &     # (as the Makefile)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene_multihit.hip -o $OBJ/scene_multihit.o &     # (as the Makefile)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c point_query.hip -o $OBJ/point_query.o &     # (as the Makefile)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c knn.hip -o $OBJ/knn.o &     # (as the Makefile)
