@@ -9,8 +9,8 @@ mkdir -p $OBJ
 cd $ROOT/hip-bvh-construction_amd/csrc
 FLAGS="${ABL--DBVH_ABLATION} -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off ${KPRELOAD--mllvm -amdgpu-kernarg-preload-count=16} -I$ROOT/include -I. -Wno-unused-value -Wno-unused-result -Wno-pass-failed"
 # (every object is rebuilt every time: a cache keyed on the .hip time stamps missed header and flag changes — ADVICE r04)
-for f in api stage_em sort misc trace batched refit refit_subset query optimize overlap split many many_ploc; do /opt/rocm/bin/hipcc $FLAGS $EXTRA -c $f.hip -o $OBJ/$f.o & done
-for f in lbvh collapse; do /opt/rocm/bin/hipcc $FLAGS -fno-honor-nans -mno-amdgpu-ieee $EXTRA -c $f.hip -o $OBJ/$f.o & done
+for f in api stage_em sort misc collapse trace batched refit refit_subset query optimize overlap split many many_ploc; do /opt/rocm/bin/hipcc $FLAGS $EXTRA -c $f.hip -o $OBJ/$f.o & done
+for f in lbvh; do /opt/rocm/bin/hipcc $FLAGS -fno-honor-nans -mno-amdgpu-ieee $EXTRA -c $f.hip -o $OBJ/$f.o & done
 for f in hploc ploc; do /opt/rocm/bin/hipcc $FLAGS -fno-honor-nans -mno-amdgpu-ieee ${NOSLP--fno-slp-vectorize} $EXTRA -c $f.hip -o $OBJ/$f.o & done     # (as the Makefile; NOSLP="" builds them with the SLP vectoriser)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene.hip -o $OBJ/scene.o &     # (as the Makefile: never with the SLP vectoriser, scene.hip says why)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene_point.hip -o $OBJ/scene_point.o &     # (as the Makefile)
