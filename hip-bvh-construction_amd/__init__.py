@@ -38,7 +38,7 @@ POINT_QUERY = np.dtype([("point", "<f4", 3), ("radius", "<f4")])                
 POINT_HIT = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("reserved", "<u4")])   # bvh_point_hit
 KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4")])                                                         # bvh_knn_hit (bvh_knn)
 KNN_MAX_K = 32
-INSTANCE_KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4")])         # bvh_instance_knn_hit (bvh_scene_knn)
+INSTANCE_KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4")])         # bvh_instance_knn_hit (bvh_scene_knn, bvh_scene_radius_search)
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
 TRANSFORMATION = np.dtype([("translation", "<f4", 3), ("pad", "<f4"), ("scale", "<f4", 3), ("pad1", "<f4"), ("quat", "<f4", 4), ("pad2", "<f4", 4)])
 assert RAY.itemsize == 32 and CAMERA.itemsize == 64 and TRANSFORMATION.itemsize == 64 and INSTANCE.itemsize == 64 and INSTANCE_HIT.itemsize == 32
@@ -78,7 +78,7 @@ EXPORTS = [
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
-    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn",
+    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
@@ -119,7 +119,7 @@ QUERY_CLOSEST, QUERY_ANY = 0, 1      # bvh_query_kind
 _QUERY_IDS = {"closest": QUERY_CLOSEST, "any": QUERY_ANY}
 OVERLAP_BOXES, OVERLAP_SELF = 0, 1   # bvh_overlap_mode
 HITS_SORTED = 1                      # BVH_HITS_SORTED (bvh_intersect_all's flag)
-RADIUS_SORTED = 1                    # BVH_RADIUS_SORTED (bvh_radius_search's flag)
+RADIUS_SORTED = 1                    # BVH_RADIUS_SORTED (bvh_radius_search's and bvh_scene_radius_search's flag)
 SPLIT_MAX_DEPTH = 16                 # BVH_SPLIT_MAX_DEPTH (bvh_split_refs)
 ABI_VERSION = 4                      # BVH_ABI_VERSION of include/bvh_mi355x.h this binding was written against
 # bvh_option (bvh_ctx_set_option) and the names this harness accepts for the values
@@ -232,6 +232,7 @@ def lib() -> C.CDLL:
         "bvh_scene_closest_point": ([vp, vp, u32, vp, i32], i32),
         "bvh_scene_knn": ([vp, vp, u32, u32, vp, vp], i32),
         "bvh_scene_intersect_all": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_scene_radius_search": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
@@ -1560,6 +1561,63 @@ class Scene:
                 hits.free(); hits = None
                 cap = total.value
             return offsets.download(np.uint32, n_rays + 1), hits.download(INSTANCE_HIT, total.value)
+        finally:
+            offsets.free()
+            if hits is not None:
+                hits.free()
+            if own is not None:
+                own.free()
+
+    def radius_search(self, points, radius=None, sorted: bool = True, count_only: bool = False, capacity: int | None = None, n_points: int | None = None):
+        """bvh_scene_radius_search: every triangle of every active instance within each query's radius.  ``points`` as for knn (a host POINT_QUERY array, a
+        host (n, 3) float array whose radius is ``radius`` (None: +inf), or a device buffer of POINT_QUERY records with ``n_points``).  Returns host arrays
+        (offsets u32[n + 1], hits INSTANCE_KNN_HIT[total]): query i's records are hits[offsets[i]:offsets[i + 1]], in ascending (dist2, instance, prim) order
+        when ``sorted`` (BVH_RADIUS_SORTED; quadratic in a slice's length), in no particular order otherwise; an empty slice is "nothing within the radius".
+        ``count_only`` returns offsets alone.  ``capacity`` None: a count-only call first, then a call with the exact capacity; a given capacity that is too
+        small is re-allocated with the total the call reported and the call repeated once."""
+        ctx = self.ctx
+        own = None
+        if isinstance(points, np.ndarray):
+            if points.dtype != POINT_QUERY:
+                xyz = np.asarray(points, dtype=np.float32)
+                if xyz.ndim != 2 or xyz.shape[1] != 3:
+                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
+                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
+                points["point"] = xyz
+                points["radius"] = np.float32(np.inf) if radius is None else np.float32(radius)
+            elif radius is not None:
+                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
+            n_points = points.shape[0]
+            own = points = ctx.upload(np.ascontiguousarray(points)) if n_points else None
+        elif n_points is None:
+            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
+            if n_points is None:
+                raise BvhError("n_points is required for device points")
+        if n_points == 0:                                 # no points: the empty answer, without a call
+            off = np.zeros(1, dtype=np.uint32)
+            return off if count_only else (off, np.zeros(0, dtype=INSTANCE_KNN_HIT))
+        flags = RADIUS_SORTED if sorted else 0
+        what = "bvh_scene_radius_search"
+        offsets = ctx.alloc((n_points + 1) * 4)
+        hits = None
+        self._sync_blas()
+        try:
+            total = C.c_uint64()
+            if count_only or capacity is None:
+                _check(lib().bvh_scene_radius_search(self.handle, _ptr(points), n_points, flags, offsets.ptr, None, 0, C.byref(total)), what)
+                if count_only:
+                    return offsets.download(np.uint32, n_points + 1)
+                cap = total.value
+            else:
+                cap = int(capacity)
+            for _ in range(2):
+                hits = ctx.alloc(max(cap, 1) * INSTANCE_KNN_HIT.itemsize)
+                _check(lib().bvh_scene_radius_search(self.handle, _ptr(points), n_points, flags, offsets.ptr, hits.ptr, cap, C.byref(total)), what)
+                if total.value <= cap:
+                    break
+                hits.free(); hits = None
+                cap = total.value
+            return offsets.download(np.uint32, n_points + 1), hits.download(INSTANCE_KNN_HIT, total.value)
         finally:
             offsets.free()
             if hits is not None:

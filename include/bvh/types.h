@@ -6,7 +6,8 @@
  *   bvh_point_query 16 B (bvh_closest_point's input)      bvh_point_hit 32 B (its output); neither has a counterpart
  *   bvh_instance_point_hit 32 B (bvh_scene_closest_point's output: bvh_point_hit with the instance in its last word); no counterpart
  *   bvh_knn_hit 8 B (one entry of bvh_knn's lists and one record of bvh_radius_search's slices; both read bvh_point_query too); no counterpart
- *   bvh_instance_knn_hit 16 B (one entry of bvh_scene_knn's lists: bvh_knn_hit with the instance, padded to one 16-byte store); no counterpart
+ *   bvh_instance_knn_hit 16 B (one entry of bvh_scene_knn's lists and one record of bvh_scene_radius_search's slices: bvh_knn_hit with the instance, padded to one
+ *     16-byte store); no counterpart
  * Usable from C, C++ and HIP device code. */
 #ifndef BVH_TYPES_H
 #define BVH_TYPES_H
@@ -41,8 +42,8 @@ typedef struct { float object_to_world[12]; uint32_t blas; uint32_t reserved[3];
 typedef struct { float t, u, v; uint32_t prim_idx, instance_idx; uint32_t reserved[3]; } bvh_instance_hit;
 /* point: the closest point of instance instance_idx's triangle prim_idx in WORLD space, dist2 = its squared world distance, (u, v) = the weights of v2 and v3 */
 typedef struct { bvh_float3 point; float dist2; float u, v; uint32_t prim_idx, instance_idx; } bvh_instance_point_hit;
-/* one entry of a scene's k-nearest list (bvh_scene_knn): the squared WORLD distance of instance instance_idx's triangle prim_idx; reserved = 0 (an unused slot:
- * {radius*radius, BVH_INVALID, BVH_INVALID, 0}) */
+/* one entry of a scene's k-nearest list (bvh_scene_knn) and one record of bvh_scene_radius_search's slices: the squared WORLD distance of instance
+ * instance_idx's triangle prim_idx; reserved = 0 (an unused slot of a k-nearest list: {radius*radius, BVH_INVALID, BVH_INVALID, 0}; a slice has no unused slots) */
 typedef struct { float dist2; uint32_t prim_idx, instance_idx, reserved; } bvh_instance_knn_hit;
 
 #ifdef __cplusplus

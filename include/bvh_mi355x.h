@@ -699,7 +699,40 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  *   errors enqueue and write nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene; NULL d_rays or d_offsets; a flag bit other than BVH_HITS_SORTED;
  *     n_rays >= 2^30; d_offsets or d_hits (capacity records, clamped to 2^32 - 1) overlapping d_rays or each other.
  *   n_rays == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
- *   bvh_ctx_kernel_times reports k_scene_hits_count, k_scene_hits_fill, k_scene_hits_deep (after each pass) and k_overlap_scan. */
+ *   bvh_ctx_kernel_times reports k_scene_hits_count, k_scene_hits_fill, k_scene_hits_deep (after each pass) and k_overlap_scan.
+ * Radius search: bvh_scene_radius_search is bvh_radius_search on a scene — EVERY triangle of every active instance within the radius of each point.  Its
+ * contract is the union of bvh_scene_closest_point's and bvh_radius_search's; nothing in it is new arithmetic (tests/test_scene_radius.py restates it in numpy).
+ *   candidate and acceptance: bvh_scene_closest_point's, word for word — the world triangle V_i = M_k v_i in the stated order, dist2 = tri_closest(V1, V2, V3, p),
+ *     accepted iff dist2 <= r2 = radius * radius in f32.  A query with a NaN coordinate, a NaN radius or radius < 0 accepts nothing.  Radius 0 (or -0) accepts
+ *     the candidates at dist2 == 0; an infinite radius accepts every triangle of every active instance whose dist2 is not NaN.  Inactive instances never answer.
+ *   answer: query i's set is ALL its accepted candidates over all active instances, in compressed-row form: d_hits[d_offsets[i] .. d_offsets[i+1]) is query
+ *     i's slice, d_offsets[0] = 0, d_offsets[n_points] = the total.  A record is a bvh_instance_knn_hit {dist2, prim_idx, instance_idx, 0}.  Each
+ *     (instance, prim) pair appears at most once per slice.  There is no padding and there are no miss records: an empty slice is a miss.  With d_hits == NULL
+ *     the call only counts.
+ *   order inside a slice: without BVH_RADIUS_SORTED unspecified, but the same call on the same arrays gives the same bytes.  With BVH_RADIUS_SORTED each slice
+ *     is ascending in (dist2, instance_idx, prim_idx), compared lexicographically — bvh_scene_knn's order; the whole d_hits array then depends on none of the
+ *     top-level builder, the BLAS builders, the layouts, the formats, the traversal order.  Any other flag bit is an error.  The sorted insertion is quadratic
+ *     in the slice's length, as for bvh_radius_search: sort long slices on the caller's side.
+ *   box tests: bvh_scene_closest_point's at both levels, against r2 for the whole walk: the bound never shrinks.  Top level: box_dist_pass on the world boxes.
+ *     Inside instance k: the mapped point p' = W_k p and the slack e, boxes grown by 2^-16 * (their largest |coordinate|) + e, a subtree culled iff
+ *     s2 * lb' * (1 - 2^-20) > r2 (a NaN product never culls).
+ *   well-conditioned (set exact): every accepted candidate of the query meets bvh_scene_closest_point's conditions (1) and (2) against its own
+ *     dist2.  On EVERY query each record is an accepted candidate of its (instance, prim) with bit-equal dist2, and the slice is a subset of the true set.
+ *   relation to the other queries: on well-conditioned queries the first min(k, count) records of a sorted slice are bvh_scene_knn's list for the same point
+ *     and k, bit for bit.  With one identity instance, (dist2, prim_idx) are bvh_radius_search's on the BLAS.
+ *   passes, capacity, total_out, saturation, asynchrony: exactly bvh_scene_intersect_all's.  The call always counts and scans; the fill decides ON THE DEVICE
+ *     whether it runs (d_hits != NULL, total <= capacity and total < 2^32); a skipped fill leaves d_hits untouched and d_offsets complete; total_out != NULL is
+ *     the only host wait (an 8-byte read-back); a total of 2^32 or more saturates d_offsets at 0xFFFFFFFF and returns BVH_E_TOO_LARGE when total_out was given
+ *     (with *total_out set); d_hits is never written outside query i's slice nor past the total.  The per-query counter saturates at 0xFFFFFFFD, so the
+ *     internal mark 0xFFFFFFFE is never a count.  The scratch words are the ctx's, the same as bvh_scene_intersect_all's; on a ctx that has no arena yet (a
+ *     one-instance scene on a fresh ctx) the first call reserves the smallest one, as bvh_ctx_reserve(ctx, 2) would.
+ *   no depth limit at either level: a query whose short stack would overflow is finished by a stackless pass through the plans the scene owns.  Both passes
+ *     test the same boxes (every record below a root; neither the top-level root's own box nor a BLAS root's, for which the instance's world box stands), so
+ *     count and fill agree on every query's set whichever pass served it.
+ *   errors enqueue and write nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene; NULL d_points or d_offsets; a flag bit other than BVH_RADIUS_SORTED;
+ *     n_points >= 2^30; d_offsets or d_hits (capacity records, clamped to 2^32 - 1) overlapping d_points or each other.
+ *   n_points == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
+ *   bvh_ctx_kernel_times reports k_scene_radius_count, k_scene_radius_fill, k_scene_radius_deep (after each pass) and k_overlap_scan. */
 typedef struct { bvh_result tree; bvh_build_input tris; } bvh_blas;   /* tris.tri_format PADDED64 with d_tris NULL: tree.d_tris is Triangle[n_leaves] */
 typedef struct bvh_scene bvh_scene;
 int  bvh_scene_create(bvh_ctx* ctx, bvh_scene** out);
@@ -713,6 +746,9 @@ int  bvh_scene_knn(bvh_scene* scene, const bvh_point_query* d_points, uint32_t n
                    bvh_instance_knn_hit* d_hits /* [n_points * k], query i's list at d_hits[i*k .. i*k+k) */, uint32_t* d_counts /* [n_points] or NULL */);
 int  bvh_scene_intersect_all(bvh_scene* scene, const bvh_ray* d_rays, uint32_t n_rays, uint32_t flags /* 0 or BVH_HITS_SORTED */,
                              uint32_t* d_offsets /* u32[n_rays + 1], device */, bvh_instance_hit* d_hits /* [capacity], device, or NULL: count only */,
+                             uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+int  bvh_scene_radius_search(bvh_scene* scene, const bvh_point_query* d_points, uint32_t n_points, uint32_t flags /* 0 or BVH_RADIUS_SORTED */,
+                             uint32_t* d_offsets /* u32[n_points + 1], device */, bvh_instance_knn_hit* d_hits /* [capacity], device, or NULL: count only */,
                              uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
 int  bvh_scene_tlas(const bvh_scene* scene, bvh_result* out);
 
