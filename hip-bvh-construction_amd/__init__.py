@@ -39,6 +39,7 @@ POINT_HIT = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v",
 KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4")])                                                         # bvh_knn_hit (bvh_knn)
 KNN_MAX_K = 32
 INSTANCE_KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4")])         # bvh_instance_knn_hit (bvh_scene_knn, bvh_scene_radius_search)
+INSTANCE_PRIM = np.dtype([("prim", "<u4"), ("instance", "<u4")])                                                   # bvh_instance_prim (bvh_scene_overlap)
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
 TRANSFORMATION = np.dtype([("translation", "<f4", 3), ("pad", "<f4"), ("scale", "<f4", 3), ("pad1", "<f4"), ("quat", "<f4", 4), ("pad2", "<f4", 4)])
 assert RAY.itemsize == 32 and CAMERA.itemsize == 64 and TRANSFORMATION.itemsize == 64 and INSTANCE.itemsize == 64 and INSTANCE_HIT.itemsize == 32
@@ -78,7 +79,7 @@ EXPORTS = [
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
-    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search",
+    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
@@ -120,6 +121,7 @@ _QUERY_IDS = {"closest": QUERY_CLOSEST, "any": QUERY_ANY}
 OVERLAP_BOXES, OVERLAP_SELF = 0, 1   # bvh_overlap_mode
 HITS_SORTED = 1                      # BVH_HITS_SORTED (bvh_intersect_all's flag)
 RADIUS_SORTED = 1                    # BVH_RADIUS_SORTED (bvh_radius_search's and bvh_scene_radius_search's flag)
+SCENE_OVERLAP_SORTED = 1             # BVH_SCENE_OVERLAP_SORTED (bvh_scene_overlap's flag)
 SPLIT_MAX_DEPTH = 16                 # BVH_SPLIT_MAX_DEPTH (bvh_split_refs)
 ABI_VERSION = 4                      # BVH_ABI_VERSION of include/bvh_mi355x.h this binding was written against
 # bvh_option (bvh_ctx_set_option) and the names this harness accepts for the values
@@ -233,6 +235,7 @@ def lib() -> C.CDLL:
         "bvh_scene_knn": ([vp, vp, u32, u32, vp, vp], i32),
         "bvh_scene_intersect_all": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_scene_radius_search": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_scene_overlap": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
@@ -1622,6 +1625,59 @@ class Scene:
             offsets.free()
             if hits is not None:
                 hits.free()
+            if own is not None:
+                own.free()
+
+    def overlap(self, boxes, sorted: bool = True, count_only: bool = False, capacity: int | None = None, n_boxes: int | None = None):
+        """bvh_scene_overlap: every (instance, triangle) pair whose mapped leaf box touches each world-space query box.  ``boxes`` is a host array of n
+        boxes ((n, 6) or (n, 2, 3) floats, or dtype AABB) or a device buffer of bvh_aabb records with ``n_boxes``.  Returns host arrays (offsets u32[n + 1],
+        records INSTANCE_PRIM[total]): query i's records are records[offsets[i]:offsets[i + 1]], in ascending (instance, prim) order when ``sorted``
+        (BVH_SCENE_OVERLAP_SORTED; quadratic in a slice's length), in no particular order otherwise; an empty slice is "touches nothing".  ``count_only``
+        returns offsets alone.  ``capacity`` None: a count-only call first, then a call with the exact capacity; a given capacity that is too small is
+        re-allocated with the total the call reported and the call repeated once."""
+        ctx = self.ctx
+        own = None
+        if isinstance(boxes, np.ndarray):
+            if boxes.dtype != AABB:
+                boxes = np.ascontiguousarray(boxes, dtype=np.float32)
+                if boxes.size % 6 or (boxes.ndim >= 2 and int(np.prod(boxes.shape[1:])) != 6):
+                    raise BvhError("boxes must have dtype AABB or 6 floats per box")
+                boxes = boxes.reshape(-1, 6)
+            n_boxes = boxes.shape[0]
+            own = boxes = ctx.upload(np.ascontiguousarray(boxes)) if n_boxes else None
+        elif n_boxes is None:
+            n_boxes = boxes.nbytes // 24 if isinstance(boxes, DeviceBuffer) else None
+            if n_boxes is None:
+                raise BvhError("n_boxes is required for device boxes")
+        if n_boxes == 0:                                  # no boxes: the empty answer, without a call
+            off = np.zeros(1, dtype=np.uint32)
+            return off if count_only else (off, np.zeros(0, dtype=INSTANCE_PRIM))
+        flags = SCENE_OVERLAP_SORTED if sorted else 0
+        what = "bvh_scene_overlap"
+        offsets = ctx.alloc((n_boxes + 1) * 4)
+        prims = None
+        self._sync_blas()
+        try:
+            total = C.c_uint64()
+            if count_only or capacity is None:
+                _check(lib().bvh_scene_overlap(self.handle, _ptr(boxes), n_boxes, flags, offsets.ptr, None, 0, C.byref(total)), what)
+                if count_only:
+                    return offsets.download(np.uint32, n_boxes + 1)
+                cap = total.value
+            else:
+                cap = int(capacity)
+            for _ in range(2):
+                prims = ctx.alloc(max(cap, 1) * INSTANCE_PRIM.itemsize)
+                _check(lib().bvh_scene_overlap(self.handle, _ptr(boxes), n_boxes, flags, offsets.ptr, prims.ptr, cap, C.byref(total)), what)
+                if total.value <= cap:
+                    break
+                prims.free(); prims = None
+                cap = total.value
+            return offsets.download(np.uint32, n_boxes + 1), prims.download(INSTANCE_PRIM, total.value)
+        finally:
+            offsets.free()
+            if prims is not None:
+                prims.free()
             if own is not None:
                 own.free()
 

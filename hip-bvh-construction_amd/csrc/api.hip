@@ -214,7 +214,7 @@ void carve(bvh_ctx* c, char* base, uint32_t cap, size_t* total) {
     c->ploc.ids1 = k.take<u32>(n);
     c->ploc.status = k.take<u64>((size_t)PLOC_MAX_ITERS * ploc_chunks(cap));
     c->ploc.state = k.take<u32>(PLOC_STATE_WORDS);
-    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's / bvh_closest_point's / bvh_knn's overflow count (bvh_overlap / bvh_intersect_all / bvh_radius_search / bvh_scene_intersect_all / bvh_scene_radius_search: [58] count pass, [59] fill pass, [60..61] u64 total)
+    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's / bvh_closest_point's / bvh_knn's overflow count (bvh_overlap / bvh_intersect_all / bvh_radius_search / bvh_scene_intersect_all / bvh_scene_radius_search / bvh_scene_overlap: [58] count pass, [59] fill pass, [60..61] u64 total)
     c->hploc.zero_parent = c->small + 1;
     c->overlap_sums = k.take<u64>(OVERLAP_SCAN_BLOCKS);
     *total = k.off;
@@ -407,7 +407,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -1782,6 +1782,55 @@ int bvh_scene_radius_search(bvh_scene* sc, const bvh_point_query* d_points, uint
     const SceneHits h{ d_offsets, d_hits, total, capacity };
     launch_scene_radius_count(s, q, h, c->overlap_sums, total);
     if (d_hits) { q.overflow = overflow + 1; launch_scene_radius_fill(s, (flags & BVH_RADIUS_SORTED) ? 1 : 0, q, h); }
+    HIP_TRY(hipGetLastError());
+    if (install.on) c->recorder.mark(s, nullptr);
+    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
+        u32* const rb = c->h_pinned + 8;
+        const int r = read_back(c, c->small + 60, 2, nullptr, 0, rb); if (r) return r;
+        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
+        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
+    }
+    return 0;
+}
+
+// bvh_overlap's query boxes on a scene, bvh_scene_radius_search's count -> scan -> fill sequence, overflow words, total word and read-back (the ctx's words);
+// every argument is checked before anything is enqueued, so an error writes nothing
+int bvh_scene_overlap(bvh_scene* sc, const bvh_aabb* d_boxes, uint32_t n_boxes, uint32_t flags, uint32_t* d_offsets, bvh_instance_prim* d_prims,
+                      uint64_t capacity, uint64_t* total_out) {
+    if (!sc || !d_boxes || !d_offsets || !sc->built) return BVH_E_INVALID_ARG;
+    if (flags & ~BVH_SCENE_OVERLAP_SORTED) return BVH_E_INVALID_ARG;
+    if (n_boxes >= (1u << 30)) return BVH_E_INVALID_ARG;
+    {   // the three caller arrays must not overlap (d_prims is never written past 2^32 - 1 records: a larger total skips the fill)
+        struct Range { uintptr_t lo, hi; };
+        const uint64_t recs = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;
+        const Range rq{ (uintptr_t)d_boxes, (uintptr_t)d_boxes + (uint64_t)n_boxes * sizeof(bvh_aabb) };
+        const Range ro{ (uintptr_t)d_offsets, (uintptr_t)d_offsets + ((uint64_t)n_boxes + 1u) * sizeof(u32) };
+        const Range rh{ (uintptr_t)d_prims, (uintptr_t)d_prims + (d_prims ? recs * sizeof(bvh_instance_prim) : 0u) };
+        auto cross = [](const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; };
+        if (cross(rq, ro) || cross(rq, rh) || cross(ro, rh)) return BVH_E_INVALID_ARG;
+    }
+    bvh_ctx* c = sc->ctx;
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    if (n_boxes == 0) {                                       // d_offsets[0] = total = 0, nothing else
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
+        if (total_out) *total_out = 0;
+        return 0;
+    }
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    // (bvh_scene_radius_search: a one-instance scene on a fresh ctx never made the arena the scratch words live in: the smallest one, nothing points into it)
+    if (!c->arena) { const int r = ensure_capacity(c, 2); if (r) return r; }
+    u32* const overflow = c->small + 58;                      // bvh_overlap's words: [0] count pass, [1] fill pass
+    u64* const total = reinterpret_cast<u64*>(c->small + 60);
+    HIP_TRY(hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s));
+    SceneQuery q;
+    q.rays = d_boxes; q.hits = d_prims; q.overflow = overflow;
+    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
+    q.n_rays = n_boxes; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
+    const SceneHits h{ d_offsets, d_prims, total, capacity };
+    launch_scene_overlap_count(s, q, h, c->overlap_sums, total);
+    if (d_prims) { q.overflow = overflow + 1; launch_scene_overlap_fill(s, (flags & BVH_SCENE_OVERLAP_SORTED) ? 1 : 0, q, h); }
     HIP_TRY(hipGetLastError());
     if (install.on) c->recorder.mark(s, nullptr);
     if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11

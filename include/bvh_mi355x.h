@@ -732,7 +732,48 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  *   errors enqueue and write nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene; NULL d_points or d_offsets; a flag bit other than BVH_RADIUS_SORTED;
  *     n_points >= 2^30; d_offsets or d_hits (capacity records, clamped to 2^32 - 1) overlapping d_points or each other.
  *   n_points == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
- *   bvh_ctx_kernel_times reports k_scene_radius_count, k_scene_radius_fill, k_scene_radius_deep (after each pass) and k_overlap_scan. */
+ *   bvh_ctx_kernel_times reports k_scene_radius_count, k_scene_radius_fill, k_scene_radius_deep (after each pass) and k_overlap_scan.
+ * Box queries: bvh_scene_overlap is bvh_overlap on a scene — which triangles' leaf boxes of which active instances does each WORLD-space query box touch.
+ * bvh_overlap(bvh_scene_tlas) alone is the broad phase (which instances); this is both phases in one call, and like bvh_overlap it is exact on EVERY query
+ * (tests/test_scene_overlap.py restates the contract in numpy).
+ *   mapped box: the mapped box of object box {lo, hi} under instance matrix M, with m_rc = object_to_world[4r + c], all in f32 without contraction; for row r
+ *     a_c = m_rc * lo.c and b_c = m_rc * hi.c (c = 0, 1, 2),
+ *     min.r = ((fminf(a_0, b_0) + fminf(a_1, b_1)) + fminf(a_2, b_2)) + m_r3,   max.r = ((fmaxf(a_0, b_0) + fmaxf(a_1, b_1)) + fmaxf(a_2, b_2)) + m_r3.
+ *     For finite values this is, as values, the componentwise fminf / fmaxf over the box's 8 corners, each mapped in the order of the scene's world box
+ *     (((m_r0 x + m_r1 y) + m_r2 z) + m_r3); it differs at most in the sign of a zero.
+ *   test: pair (instance k, primitive j) passes query box q iff instance k is active, primitive j's leaf box b is valid (b.min <= b.max on every axis; the leaf
+ *     box is layout 0's node n-1+j or layout 1's d_leaves[j].aabb, as bvh_overlap defines it) and box_overlap(q, mapped(M_k, b)) with bvh_overlap's closed,
+ *     comparisons-only test: touching boxes overlap, a NaN anywhere fails, an inverted q overlaps nothing.
+ *   answer: query i's set is EVERY passing pair, in compressed-row form: d_prims[d_offsets[i] .. d_offsets[i+1]) is query i's slice, d_offsets[0] = 0,
+ *     d_offsets[n_boxes] = the total.  A record is a bvh_instance_prim {prim_idx, instance_idx}.  Each pair appears at most once per slice.  There are no miss
+ *     records: an empty slice is a miss.  With d_prims == NULL the call only counts.
+ *   order inside a slice: without BVH_SCENE_OVERLAP_SORTED unspecified, but the same call on the same arrays gives the same bytes.  With
+ *     BVH_SCENE_OVERLAP_SORTED each slice is ascending in (instance_idx, prim_idx); the whole d_prims array then depends on none of the top-level builder, the
+ *     BLAS builders, the layouts, the traversal order.  Any other flag bit is an error.  The sorted insertion is quadratic in the slice's length, as for the
+ *     siblings: sort long slices on the caller's side.
+ *   exactness: the set is exact for EVERY query — there is no well-conditioned share — whenever (1) every internal box of every BLAS contains its children's
+ *     boxes (true bitwise of every tree the library makes, and after bvh_refit and bvh_optimize) and (2) every mapped value is finite.  Rounded f32
+ *     multiplication by a fixed factor and rounded addition are monotone, so min.r / max.r are monotone in lo / hi, so a parent's mapped box contains its
+ *     children's mapped boxes as values, so the instance's stored world box (the 8 mapped corners of the BLAS root box) contains everything below it; the
+ *     top-level tree's containment is bitwise as before.  When (1) or (2) fails, every reported pair still passes its own test and the
+ *     slice is a subset of the true set.
+ *   walk tests: the top level uses box_overlap on the top-level nodes and the world boxes (one instance: its world box).  Inside an instance the test above —
+ *     validity of the object box, then box_overlap against its mapped box — is applied to every record below the BLAS root; the BLAS root's own box is not
+ *     tested: the world box stands for it.
+ *   relation to the other queries: with one identity instance the prim sets equal bvh_overlap's on the BLAS for every query (((1 x + 0 y) + 0 z) + 0 == x as a
+ *     value).  The instances that appear in query i's slice are a subset of slice i of bvh_overlap on bvh_scene_tlas.
+ *   passes, capacity, total_out, saturation, asynchrony: exactly bvh_scene_radius_search's.  The call always counts and scans; the fill decides ON THE DEVICE
+ *     whether it runs (d_prims != NULL, total <= capacity and total < 2^32); a skipped fill leaves d_prims untouched and d_offsets complete; total_out != NULL
+ *     is the only host wait (an 8-byte read-back); a total of 2^32 or more saturates d_offsets at 0xFFFFFFFF and returns BVH_E_TOO_LARGE when total_out was
+ *     given (with *total_out set); d_prims is never written outside query i's slice nor past the total.  The per-query counter saturates at 0xFFFFFFFD, so the
+ *     internal mark 0xFFFFFFFE is never a count.  The scratch words are the ctx's, the same as bvh_scene_radius_search's; on a ctx that has no arena yet (a
+ *     one-instance scene on a fresh ctx) the first call reserves the smallest one, as bvh_ctx_reserve(ctx, 2) would.
+ *   no depth limit at either level: a query whose short stack would overflow is finished by a stackless pass through the plans the scene owns.  Both passes
+ *     test the same boxes, so count and fill agree on every query's set whichever pass served it.
+ *   errors enqueue and write nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene; NULL d_boxes or d_offsets; a flag bit other than
+ *     BVH_SCENE_OVERLAP_SORTED; n_boxes >= 2^30; d_offsets or d_prims (capacity records, clamped to 2^32 - 1) overlapping d_boxes or each other.
+ *   n_boxes == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
+ *   bvh_ctx_kernel_times reports k_scene_overlap_count, k_scene_overlap_fill, k_scene_overlap_deep (after each pass) and k_overlap_scan. */
 typedef struct { bvh_result tree; bvh_build_input tris; } bvh_blas;   /* tris.tri_format PADDED64 with d_tris NULL: tree.d_tris is Triangle[n_leaves] */
 typedef struct bvh_scene bvh_scene;
 int  bvh_scene_create(bvh_ctx* ctx, bvh_scene** out);
@@ -750,6 +791,10 @@ int  bvh_scene_intersect_all(bvh_scene* scene, const bvh_ray* d_rays, uint32_t n
 int  bvh_scene_radius_search(bvh_scene* scene, const bvh_point_query* d_points, uint32_t n_points, uint32_t flags /* 0 or BVH_RADIUS_SORTED */,
                              uint32_t* d_offsets /* u32[n_points + 1], device */, bvh_instance_knn_hit* d_hits /* [capacity], device, or NULL: count only */,
                              uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+#define BVH_SCENE_OVERLAP_SORTED 1u
+int  bvh_scene_overlap(bvh_scene* scene, const bvh_aabb* d_boxes, uint32_t n_boxes, uint32_t flags /* 0 or BVH_SCENE_OVERLAP_SORTED */,
+                       uint32_t* d_offsets /* u32[n_boxes + 1], device */, bvh_instance_prim* d_prims /* [capacity], device, or NULL: count only */,
+                       uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
 int  bvh_scene_tlas(const bvh_scene* scene, bvh_result* out);
 
 /* ---- stage-level entry points (one per reference kernel / library call on the path) -------------------------- */

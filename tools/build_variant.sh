@@ -17,6 +17,7 @@ for f in hploc ploc; do /opt/rocm/bin/hipcc $FLAGS -fno-honor-nans -mno-amdgpu-i
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene_knn.hip -o $OBJ/scene_knn.o &     # (as the Makefile)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene_multihit.hip -o $OBJ/scene_multihit.o &     # (as the Makefile)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene_radius.hip -o $OBJ/scene_radius.o &     # (as the Makefile)
+/opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene_overlap.hip -o $OBJ/scene_overlap.o &     # (as the Makefile)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c point_query.hip -o $OBJ/point_query.o &     # (as the Makefile)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c knn.hip -o $OBJ/knn.o &     # (as the Makefile)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c multihit.hip -o $OBJ/multihit.o &     # (as the Makefile)
