@@ -36,6 +36,7 @@ INSTANCE_HIT = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4
 INSTANCE_POINT_HIT = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("instance", "<u4")])   # bvh_instance_point_hit
 POINT_QUERY = np.dtype([("point", "<f4", 3), ("radius", "<f4")])                                               # bvh_point_query (bvh_closest_point)
 POINT_HIT = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("reserved", "<u4")])   # bvh_point_hit
+WINDING_MOMENT = np.dtype([("a", "<f4", 3), ("area", "<f4"), ("p", "<f4", 3), ("r", "<f4")])                               # bvh_winding_moment (bvh_winding_prepare)
 KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4")])                                                         # bvh_knn_hit (bvh_knn)
 KNN_MAX_K = 32
 INSTANCE_KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4")])         # bvh_instance_knn_hit (bvh_scene_knn, bvh_scene_radius_search)
@@ -81,6 +82,7 @@ EXPORTS = [
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
+    "bvh_winding_prepare", "bvh_winding_number",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
 
@@ -241,6 +243,8 @@ def lib() -> C.CDLL:
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_intersect_all": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_radius_search": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_winding_prepare": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp], i32),
+        "bvh_winding_number": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, vp, u32, C.c_float, vp], i32),
         "bvh_split_refs": ([vp, C.POINTER(BuildInput), u32, C.c_float, u32, vp, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_remap_leaves": ([vp, C.POINTER(Result), vp, u32], i32),
         "bvh_build_many": ([vp, i32, C.POINTER(BuildInput), u32, vp, u32, C.POINTER(ManyOut), C.POINTER(Timings)], i32),
@@ -726,6 +730,7 @@ class _Builder:
         self.m_timer = {}
         self._ctx = None
         self._split = None                                # build_split's device arrays: {"tris", "offsets", "ref_boxes", "ref_prims", "n_tris", "total"}
+        self._winding = None                              # winding_prepare's (triangle key, moments DeviceBuffer) of the current tree
 
     def build(self, context: Context, primitives, on_device: bool = False, n: int | None = None) -> "_Builder":
         """``primitives``: numpy array of dtype TRIANGLE (host; copied H2D untimed like the reference) or, with
@@ -812,6 +817,7 @@ class _Builder:
             if n_map is None:
                 raise BvhError("n_map is required for device maps")
         try:
+            self._free_winding()                          # (the leaves name other primitives)
             _check(lib().bvh_remap_leaves(self._ctx.handle, C.byref(self.result), _ptr(map) or None, int(n_map)), f"{ALGO_NAMES[self.ALGO]}::remap_leaves")
         finally:
             if own is not None:
@@ -976,6 +982,87 @@ class _Builder:
             hits.free()
             if own is not None:
                 own.free()
+
+    def _free_winding(self) -> None:
+        if self._winding is not None:
+            self._winding[1].free()
+            self._winding = None
+
+    def _winding_input(self, tris, vertices, indices, n_vertices, tri_format):
+        """(key, BuildInput or None) of the triangles a winding call names, as intersect's"""
+        if tris is None and vertices is None and indices is None and self._split is not None:
+            tris, tri_format = self._split["tris"], TRI_PADDED64      # (a build_split tree has no d_tris of its own)
+        if tris is None and vertices is None and indices is None:
+            return None, None
+        key = (int(tri_format), _ptr(tris), _ptr(vertices), _ptr(indices), int(n_vertices))
+        return key, BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                               _ptr(indices) if indices is not None else None, n_vertices, 0)
+
+    def winding_prepare(self, tris=None, vertices=None, indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64) -> DeviceBuffer:
+        """bvh_winding_prepare on this builder's tree: the per-node moments (WINDING_MOMENT[n_leaves - 1]) in a device buffer the builder keeps and returns.
+        Triangles as for intersect.  build* / refit* / optimize / remap_leaves free the buffer: the moments of the old tree are stale."""
+        if self._ctx is None:
+            raise BvhError("winding_prepare needs a built tree")
+        key, inp = self._winding_input(tris, vertices, indices, n_vertices, tri_format)
+        self._free_winding()
+        buf = self._ctx.alloc((self.result.n_leaves - 1) * WINDING_MOMENT.itemsize)
+        try:
+            _check(lib().bvh_winding_prepare(self._ctx.handle, C.byref(self.result), C.byref(inp) if inp is not None else None, buf.ptr),
+                   f"{ALGO_NAMES[self.ALGO]}::winding_prepare")
+        except Exception:
+            buf.free()
+            raise
+        self._winding = (key, buf)
+        return buf
+
+    def winding_number(self, points, beta: float = 2.0, tris=None, vertices=None, indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64,
+                       n_points: int | None = None) -> np.ndarray:
+        """bvh_winding_number on this builder's tree: ``points`` a host (n, 3) float array, a host POINT_QUERY array (the radius is ignored) or a device buffer
+        of POINT_QUERY records (DeviceBuffer / int address, with ``n_points``); returns f32[n].  Prepares the moments on first use, and again when other
+        triangles are named than the kept moments were made from."""
+        if self._ctx is None:
+            raise BvhError("winding_number needs a built tree")
+        ctx = self._ctx
+        key, inp = self._winding_input(tris, vertices, indices, n_vertices, tri_format)
+        if self._winding is None or self._winding[0] != key:
+            self.winding_prepare(tris, vertices, indices, n_vertices, tri_format)
+        own = None
+        if isinstance(points, np.ndarray):
+            if points.dtype != POINT_QUERY:
+                xyz = np.asarray(points, dtype=np.float32)
+                if xyz.ndim != 2 or xyz.shape[1] != 3:
+                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
+                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
+                points["point"] = xyz
+            n_points = points.shape[0]
+            own = points = ctx.upload(np.ascontiguousarray(points)) if n_points else None
+        elif n_points is None:
+            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
+            if n_points is None:
+                raise BvhError("n_points is required for device points")
+        if n_points == 0:
+            return np.empty(0, dtype=np.float32)
+        w = ctx.alloc(n_points * 4)
+        try:
+            _check(lib().bvh_winding_number(ctx.handle, C.byref(self.result), C.byref(inp) if inp is not None else None, self._winding[1].ptr, _ptr(points),
+                                            n_points, float(beta), w.ptr), f"{ALGO_NAMES[self.ALGO]}::winding_number")
+            return w.download(np.float32, n_points)
+        finally:
+            w.free()
+            if own is not None:
+                own.free()
+
+    def signed_distance(self, points, beta: float = 2.0, tris=None, vertices=None, indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64):
+        """-> (sd f32[n], hits POINT_HIT[n]): closest_point's distance sqrt(dist2) (unbounded radius), negated where winding_number > 0.5 (inside).  ``points``: a
+        host (n, 3) float array or POINT_QUERY records (their radius is replaced by +inf).  Plain composition of the two calls."""
+        if isinstance(points, np.ndarray) and points.dtype == POINT_QUERY:
+            points = np.ascontiguousarray(points["point"])
+        xyz = np.asarray(points, dtype=np.float32)
+        hits = self.closest_point(xyz, tris=tris, vertices=vertices, indices=indices, n_vertices=n_vertices, tri_format=tri_format)
+        w = self.winding_number(xyz, beta=beta, tris=tris, vertices=vertices, indices=indices, n_vertices=n_vertices, tri_format=tri_format)
+        with np.errstate(invalid="ignore"):
+            d = np.sqrt(hits["dist2"])
+            return np.where(w > np.float32(0.5), -d, d).astype(np.float32), hits
 
     def knn(self, points, k: int, radius=None, tris=None, vertices=None, indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64,
             n_points: int | None = None):
@@ -1193,6 +1280,7 @@ class _Builder:
                 own.free()
 
     def _publish(self) -> "_Builder":
+        self._free_winding()                              # (a build, refit or optimise: the kept winding moments are stale)
         r, t = self.result, self.timings
         self.m_rootNodeIdx, self.m_nInternalNodes = r.root, r.n_internal
         self.d_bvhNodes, self.d_leafNodes = r.d_nodes, r.d_leaves

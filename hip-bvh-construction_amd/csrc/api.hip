@@ -214,7 +214,7 @@ void carve(bvh_ctx* c, char* base, uint32_t cap, size_t* total) {
     c->ploc.ids1 = k.take<u32>(n);
     c->ploc.status = k.take<u64>((size_t)PLOC_MAX_ITERS * ploc_chunks(cap));
     c->ploc.state = k.take<u32>(PLOC_STATE_WORDS);
-    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's / bvh_closest_point's / bvh_knn's overflow count (bvh_overlap / bvh_intersect_all / bvh_radius_search / bvh_scene_intersect_all / bvh_scene_radius_search / bvh_scene_overlap: [58] count pass, [59] fill pass, [60..61] u64 total)
+    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's / bvh_closest_point's / bvh_knn's / bvh_winding_number's overflow count (bvh_overlap / bvh_intersect_all / bvh_radius_search / bvh_scene_intersect_all / bvh_scene_radius_search / bvh_scene_overlap: [58] count pass, [59] fill pass, [60..61] u64 total)
     c->hploc.zero_parent = c->small + 1;
     c->overlap_sums = k.take<u64>(OVERLAP_SCAN_BLOCKS);
     *total = k.off;
@@ -407,7 +407,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_point_query(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_point_query(); warm_winding(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -928,6 +928,80 @@ int bvh_closest_point(bvh_ctx* c, const bvh_result* tree, const bvh_build_input*
     if (e == hipSuccess) {
         launch_closest_point(s, (int)tree->layout, query, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_points, n_points,
                              tree->d_nodes, tree->d_leaves, tree->n_leaves, tree->root, d_hits, overflow, c->parent);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
+    if (install.on) c->recorder.mark(s, nullptr);
+    return 0;
+}
+
+// ---- winding numbers (no counterpart in the reference) ----------------------------------------------------------------------------------------------
+// the tree / triangle checks of query_check and the moments array's own; every argument is checked before anything is enqueued, so an error writes nothing.
+// rg / n_rg: the byte ranges of the tree's and the triangles' arrays, which neither d_moments nor an answer array may overlap
+struct WindRange { uintptr_t lo, hi; };
+static bool wind_overlaps(const WindRange* rg, int n_rg, const void* p, uint64_t bytes) {
+    const uintptr_t lo = (uintptr_t)p, hi = lo + bytes;
+    for (int k = 0; k < n_rg; ++k) if (bytes && rg[k].lo < rg[k].hi && lo < rg[k].hi && rg[k].lo < hi) return true;
+    return false;
+}
+static int winding_check(const bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const void* d_moments, bvh_build_input* in, WindRange* rg, int* n_rg) {
+    if (!c || !tree || !d_moments || ((uintptr_t)d_moments & 15u)) return BVH_E_INVALID_ARG;
+    const uint32_t n = tree->n_leaves;
+    if (n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1) return BVH_E_INVALID_ARG;
+    std::memset(in, 0, sizeof *in);
+    if (tris) { if (stage_extents_valid(tris)) return BVH_E_INVALID_ARG; *in = *tris; }
+    else { if (!tree->d_tris) return BVH_E_INVALID_ARG; in->tri_format = BVH_TRI_PADDED64; in->d_tris = tree->d_tris; }
+    if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan and the exchange words live in the arena: bvh_ctx_reserve first)
+    int k = 0;
+    auto add = [&](const void* p, uint64_t bytes) { rg[k].lo = (uintptr_t)p; rg[k].hi = rg[k].lo + bytes; ++k; };
+    add(tree->d_nodes, (uint64_t)(tree->layout == 0u ? 2ull * n - 1 : n - 1ull) * sizeof(bvh2_node));
+    if (tree->layout == 1u) add(tree->d_leaves, (uint64_t)n * sizeof(bvh_primref));
+    if (in->tri_format == BVH_TRI_INDEXED) { add(in->d_vertices, (uint64_t)in->n_vertices * 12u); add(in->d_indices, (uint64_t)n * 12u); }
+    else add(in->d_tris, (uint64_t)n * (in->tri_format == BVH_TRI_PACKED36 ? 36u : 64u));
+    *n_rg = k;
+    if (wind_overlaps(rg, k, d_moments, (uint64_t)(n - 1) * sizeof(bvh_winding_moment))) return BVH_E_INVALID_ARG;
+    return 0;
+}
+
+// bvh_refit's plan (cached under its rule), then the climb on the self-cleaning flags words (begin_emit / end_emit as for a refit) and the finalise
+int bvh_winding_prepare(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, bvh_winding_moment* d_moments) {
+    bvh_build_input in; WindRange rg[4]; int n_rg = 0;
+    int r = winding_check(c, tree, tris, d_moments, &in, rg, &n_rg); if (r) return r;
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    r = begin_emit(c); if (r) return r;
+    query_plan(c, tree, s);
+    launch_winding_prepare(s, (int)tree->layout, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, tree->d_nodes, tree->d_leaves,
+                           tree->n_leaves, c->parent, c->flags, d_moments);
+    r = end_emit(c); if (r) { c->plan_serial = 0; return r; }
+    if (install.on) c->recorder.mark(s, nullptr);
+    return 0;
+}
+
+// bvh_closest_point's plan and launch sequence (its overflow word: calls on one stream are ordered)
+int bvh_winding_number(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_winding_moment* d_moments, const bvh_point_query* d_points,
+                       uint32_t n_points, float beta, float* d_w) {
+    bvh_build_input in; WindRange rg[6]; int n_rg = 0;
+    int r = winding_check(c, tree, tris, d_moments, &in, rg, &n_rg); if (r) return r;
+    if (!d_points || !d_w || !(beta >= 0.0f)) return BVH_E_INVALID_ARG;     // (a NaN beta fails the comparison)
+    const uint64_t p_bytes = (uint64_t)n_points * sizeof(bvh_point_query), w_bytes = (uint64_t)n_points * sizeof(float);
+    rg[n_rg].lo = (uintptr_t)d_moments; rg[n_rg].hi = rg[n_rg].lo + (uint64_t)(tree->n_leaves - 1) * sizeof(bvh_winding_moment); ++n_rg;
+    if (wind_overlaps(rg + n_rg - 1, 1, d_points, p_bytes)) return BVH_E_INVALID_ARG;
+    rg[n_rg].lo = (uintptr_t)d_points; rg[n_rg].hi = rg[n_rg].lo + p_bytes; ++n_rg;
+    if (wind_overlaps(rg, n_rg, d_w, w_bytes)) return BVH_E_INVALID_ARG;
+    if (n_points == 0) return 0;
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    query_plan(c, tree, s);
+    u32* overflow = c->small + 58;                            // queries left to the stackless pass
+    hipError_t e = hipMemsetAsync(overflow, 0, sizeof(u32), s);
+    if (e == hipSuccess) {
+        launch_winding(s, (int)tree->layout, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_points, n_points, tree->d_nodes,
+                       tree->d_leaves, tree->n_leaves, tree->root, d_moments, beta, d_w, overflow, c->parent);
         e = hipGetLastError();
     }
     if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }

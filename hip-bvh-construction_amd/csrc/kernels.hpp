@@ -182,6 +182,16 @@ void launch_closest_point(hipStream_t s, int layout, int query, int tri_format, 
                           uint32_t n_vertices, const void* d_points, uint32_t n_points, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root,
                           void* d_hits, uint32_t* d_overflow, const uint32_t* d_parent);
 
+// ---- winding numbers (winding.hip).  launch_winding_prepare: k_winding_climb (the seven raw sums of every internal node into d_moments, bvh_winding_moment[n-1],
+// through the parent plan of launch_refit_plan and the flags words of launch_refit_climb, all-INVALID before and left so) + k_winding_finish (first moment ->
+// centre and radius).  launch_winding: k_winding (short stack; marks a query it leaves in d_w[i]) + k_winding_deep (stackless, returns at once while
+// *d_overflow == 0); tree / triangle / point arguments as launch_closest_point's, d_w: f32[n_points]
+void launch_winding_prepare(hipStream_t s, int layout, int tri_format, const void* d_tris, const void* d_vertices, const void* d_indices, uint32_t n_vertices,
+                            const void* d_nodes, const void* d_leaves, uint32_t n, const uint32_t* d_parent, uint32_t* d_flags, void* d_moments);
+void launch_winding(hipStream_t s, int layout, int tri_format, const void* d_tris, const void* d_vertices, const void* d_indices, uint32_t n_vertices,
+                    const void* d_points, uint32_t n_points, const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root, const void* d_moments,
+                    float beta, float* d_w, uint32_t* d_overflow, const uint32_t* d_parent);
+
 // ---- k-nearest queries (knn.hip): bvh_knn's two kernels, arguments as launch_closest_point's (d_hits: bvh_knn_hit[n_points * k], query i's list at i * k;
 // d_counts: u32[n_points] or null; 1 <= k <= KNN_MAX_K).  k_knn (short stack, marks a query it leaves in d_hits[i * k].prim_idx) and k_knn_deep (stackless,
 // returns at once while *d_overflow == 0)
@@ -329,6 +339,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_point_query(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

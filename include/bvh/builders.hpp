@@ -213,6 +213,17 @@ public:
               "closestPoint");
     }
 
+    // beyond the reference (bvh_winding_prepare / bvh_winding_number): the generalized winding number of each point (1 inside a closed, outward-oriented mesh,
+    // 0 outside), against the same tree and triangles as intersect.  d_moments: caller-owned bvh_winding_moment[n_leaves - 1], 16-byte aligned; prepare again
+    // after a refit, an optimise or a rebuild.  The sign of a distance field: closestPoint's distance, negated where w > 0.5
+    void windingPrepare(Context& context, bvh_winding_moment* d_moments) {
+        check(bvh_winding_prepare(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, d_moments), "windingPrepare");
+    }
+    void windingNumber(Context& context, const bvh_winding_moment* d_moments, const bvh_point_query* d_points, u32 n, float beta, float* d_w) {
+        check(bvh_winding_number(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, d_moments, d_points, n, beta, d_w),
+              "windingNumber");
+    }
+
     // beyond the reference (bvh_knn): the k nearest triangles within each query's radius, as k (dist2, prim) records per query in ascending order (unused
     // slots {r2, BVH_INVALID}) and, with d_counts, the lists' lengths; against the same tree and triangles as intersect
     void knn(Context& context, const bvh_point_query* d_points, u32 n, u32 k, bvh_knn_hit* d_hits, u32* d_counts = nullptr) {

@@ -349,7 +349,7 @@ int  bvh_intersect_all(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_inp
 
 /* ---- point queries (no counterpart in the reference) -----------------------------------------------------------------------------------
  * Which point of the mesh is nearest to each query point within its radius (BVH_QUERY_CLOSEST), or is any triangle within the radius (BVH_QUERY_ANY)?  One
- * bvh_point_hit per query: d_hits[i] answers d_points[i].  Unsigned distance fields, proximity tests, projection onto a surface, ICP correspondences.
+ * bvh_point_hit per query: d_hits[i] answers d_points[i].  Unsigned distance fields (the sign is bvh_winding_number's), proximity tests, projection onto a surface, ICP correspondences.
  * tree / tris: exactly as bvh_intersect — any bvh_result in either layout (a build's, a refit's, an optimised or a caller-filled one on the ctx's device),
  * triangles in any bvh_tri_format (NULL: tree->d_tris is read as Triangle[n_leaves]); the same validation; arrays that are not a tree end in finite time.
  * Candidate: Ericson's ClosestPtPointTriangle (Real-Time Collision Detection, 5.1.5) in f32, operation for operation, no contraction, a = v1, b = v2, c = v3;
@@ -376,6 +376,55 @@ int  bvh_intersect_all(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_inp
  * the plan is made, k_refit_plan. */
 int  bvh_closest_point(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
                        const bvh_point_query* d_points, uint32_t n_points, bvh_point_hit* d_hits, int query /* bvh_query_kind */);
+
+/* ---- winding numbers (no counterpart in the reference) -----------------------------------------------------------------------------------
+ * Is each query point inside the mesh?  The generalized winding number w(q) = the sum over the triangles of their signed solid angle seen from q, over 4 pi: 1
+ * inside a closed, outward-oriented mesh, 0 outside, and a smooth function in between on meshes with holes, on triangle soups and on open scans.  Point-in-mesh
+ * (w > 0.5), the SIGN of a distance field (bvh_closest_point's distance, negated where w > 0.5), voxelisation and fill, repair of open scans.  Evaluated
+ * hierarchically as in Barill et al., "Fast winding numbers for soups and clouds" (2018): a far subtree contributes one dipole term, a near one is opened.
+ * Flat trees only (no scenes).  Two calls: bvh_winding_prepare once per tree, bvh_winding_number per batch of points.
+ * tree / tris: exactly as bvh_closest_point — any bvh_result in either layout (a build's, a refit's, an optimised or a caller-filled one on the ctx's device),
+ * triangles in any bvh_tri_format validated as by bvh_build_ex (NULL: tree->d_tris is read as Triangle[n_leaves]).  Nothing in the tree is written.  A
+ * primitive or child index out of range is skipped (it contributes nothing); arrays that are not a tree end in finite time with unspecified answers.
+ * All arithmetic below is f32 without contraction unless stated; every dot product is (x*x' + y*y') + z*z' and cross(u, v) = (uy*vz - uz*vy, uz*vx - ux*vz,
+ * ux*vy - uy*vx); divisions and square roots are correctly rounded.
+ *
+ * bvh_winding_prepare writes one bvh_winding_moment per internal node: d_moments[i] belongs to node i, i in [0, n_leaves - 1).
+ *   leaf (triangle a, b, c = v1, v2, v3): A = 0.5f * cross(b - a, c - a); area = sqrtf((Ax*Ax + Ay*Ay) + Az*Az); centroid c = ((a + b) + c) * (1.0f / 3.0f)
+ *     per component; first moment M = area * c.
+ *   internal node: A, area and M are the sums left + right of its children's values, componentwise, in that order.  The sums follow the tree and not the order
+ *     in which the threads arrive, so the record is a function of the tree and the triangles alone and is bit-reproducible.
+ *   p = M / area per component; if area is 0 or not finite, p = (lo + hi) * 0.5f per axis, the centre of the node's stored box.
+ *   r = sqrtf((x*x + y*y) + z*z) with, per axis, the larger of |lo - p| and |hi - p| (a NaN side is ignored): the distance from p to the farthest corner of the box.
+ *   The record is {Ax, Ay, Az, area, px, py, pz, r}.  d_moments is caller-owned device memory, 16-byte aligned.
+ *   The moments describe the tree's topology, its boxes and the triangles at the time of the call: after a refit, an optimise or a rebuild they are STALE and
+ *   the caller prepares again.  bvh_winding_number does not and cannot check this.
+ *
+ * bvh_winding_number answers d_points[i] (its radius is ignored) with d_w[i].  The walk starts at the root, which is always opened; an opened node's children
+ * are taken left first:
+ *   a leaf child adds the Van Oosterom–Strackee solid angle of its triangle: a, b, c = v1 - q, v2 - q, v3 - q; num = dot(a, cross(b, c)); la, lb, lc =
+ *     sqrtf(dot(a, a)), ...; den = (((la*lb)*lc + dot(a, b)*lc) + dot(b, c)*la) + dot(c, a)*lb; term = (2.0f * atan2f(num, den)) / FOURPI, FOURPI = 4 pi
+ *     rounded to f32.
+ *   an internal child with record {A, area, p, r}: d = p - q; d2 = (dx*dx + dy*dy) + dz*dz; t = beta * r.  The child is APPROXIMATED iff d2 > t * t — false
+ *     on NaN, so beta = +inf opens everything and the answer is then the plain sum over all triangles.  Its term is dot(A, d) / ((FOURPI * d2) * sqrtf(d2)).
+ *     Otherwise the child is opened.
+ *   The f32 terms are accumulated in f64 (the summation order is not part of the contract) and the sum is stored as f32.  A NaN answer is stored as the quiet NaN
+ *   0x7FC00000.  A query with a NaN coordinate writes that NaN.
+ * beta trades accuracy for speed: 2 is Barill et al.'s default; larger opens more (DESIGN.md §8s has measured errors).  The decision and every term are stated
+ * above, so an answer depends on the tree, the triangles and the moments only — not on the scheduler — up to the rounding of the f64 sum and of atan2f.
+ * Errors (nothing is written or enqueued, BVH_E_INVALID_ARG): NULL ctx / tree / d_moments (and, for the query, NULL d_points / d_w), n_leaves < 2, layout not 0 or
+ * 1, NULL d_nodes, layout 1 with NULL d_leaves, root not an internal node, no triangles (tris NULL and tree->d_tris NULL) or a tris format error, n_leaves larger
+ * than the ctx's capacity (the parent plan and the exchange words live in the arena; call bvh_ctx_reserve first), d_moments not 16-byte aligned, d_moments
+ * overlapping a node, leaf, triangle, vertex or index array of the call; for the query also beta < 0 or NaN, d_moments overlapping d_points or d_w, and d_w
+ * overlapping d_points or any tree or triangle array.  n_points == 0: 0, nothing is touched.
+ * Asynchronous on the ctx's stream, no read-back.  There is no depth limit: queries whose short stack would overflow are finished by a stackless pass through
+ * bvh_refit's parent plan, cached for the ctx's own tree as for bvh_intersect; the climb of bvh_winding_prepare uses the same plan.  bvh_ctx_kernel_times
+ * reports k_winding_climb and k_winding_finish (prepare), k_winding and k_winding_deep (query) and, when the plan is made, k_refit_plan. */
+int  bvh_winding_prepare(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
+                         bvh_winding_moment* d_moments /* [n_leaves - 1], device, caller-owned */);
+int  bvh_winding_number(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
+                        const bvh_winding_moment* d_moments, const bvh_point_query* d_points /* radius ignored */, uint32_t n_points, float beta,
+                        float* d_w /* f32[n_points], device */);
 
 /* ---- k-nearest queries (no counterpart in the reference) -------------------------------------------------------------------------------
  * Which k triangles are nearest to each query point within its radius?  k (dist2, prim_idx) records per query: query i's list is d_hits[i*k .. i*k+k).
