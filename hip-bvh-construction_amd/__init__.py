@@ -82,7 +82,7 @@ EXPORTS = [
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
-    "bvh_winding_prepare", "bvh_winding_number",
+    "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
 
@@ -121,6 +121,7 @@ TRI_PADDED64, TRI_PACKED36, TRI_INDEXED = 0, 1, 2
 QUERY_CLOSEST, QUERY_ANY = 0, 1      # bvh_query_kind
 _QUERY_IDS = {"closest": QUERY_CLOSEST, "any": QUERY_ANY}
 OVERLAP_BOXES, OVERLAP_SELF = 0, 1   # bvh_overlap_mode
+TRIS_QUERY, TRIS_SELF = 0, 1         # bvh_tris_mode (bvh_intersect_tris)
 HITS_SORTED = 1                      # BVH_HITS_SORTED (bvh_intersect_all's flag)
 RADIUS_SORTED = 1                    # BVH_RADIUS_SORTED (bvh_radius_search's and bvh_scene_radius_search's flag)
 SCENE_OVERLAP_SORTED = 1             # BVH_SCENE_OVERLAP_SORTED (bvh_scene_overlap's flag)
@@ -241,6 +242,7 @@ def lib() -> C.CDLL:
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_intersect_tris": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(BuildInput), u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_intersect_all": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_radius_search": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_winding_prepare": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp], i32),
@@ -1146,6 +1148,80 @@ class _Builder:
             for _ in range(2):
                 prims = ctx.alloc(cap * 4)
                 _check(lib().bvh_overlap(ctx.handle, C.byref(self.result), _ptr(boxes), n, mode, offsets.ptr, prims.ptr, cap, C.byref(total)), what)
+                if total.value <= cap:
+                    break
+                prims.free(); prims = None
+                cap = total.value
+            return offsets.download(np.uint32, n + 1), prims.download(np.uint32, total.value)
+        finally:
+            offsets.free()
+            if prims is not None:
+                prims.free()
+            if own is not None:
+                own.free()
+
+    def intersect_tris(self, other=None, self_pairs: bool = False, capacity: int | None = None, tri_format: int = TRI_PADDED64, vertices=None, indices=None,
+                       n_vertices: int = 0, n: int | None = None, tree_tris=None, tree_vertices=None, tree_indices=None, tree_n_vertices: int = 0,
+                       tree_tri_format: int = TRI_PADDED64):
+        """bvh_intersect_tris on this builder's tree: which of the tree's triangles each triangle of another mesh properly crosses.  ``other`` a host TRIANGLE
+        array, a host (m, 9) or (m, 3, 3) float array (uploaded as TRI_PACKED36), or a device buffer of records in ``tri_format`` (DeviceBuffer / int address,
+        with ``n``); ``vertices`` / ``indices`` / ``n_vertices`` / ``n`` name a device TRI_INDEXED mesh instead.  ``self_pairs=True`` is BVH_TRIS_SELF: no other
+        mesh, the tree's own triangles against each other, every unordered pair once (j > i); refused on a build_split tree, which has more leaves than
+        triangles (pass the mesh as ``other`` there).  The tree's triangles are its d_tris unless tree_tris /
+        tree_vertices / tree_indices give device inputs in ``tree_tri_format`` as for intersect.  Returns host arrays (offsets u32[m + 1], prims u32[total]):
+        query triangle i crosses prims[offsets[i]:offsets[i + 1]], in no particular order.  ``capacity`` is the first guess of the total (default 1 per
+        query); when it is too small the call is repeated with the total it reported."""
+        if self._ctx is None:
+            raise BvhError("intersect_tris needs a built tree")
+        ctx = self._ctx
+        own = None
+        qin = None
+        if self_pairs:
+            if other is not None or vertices is not None or indices is not None:
+                raise BvhError("self_pairs=True takes no other mesh")
+            if self._split is not None:
+                # (BVH_TRIS_SELF reads triangle i for every i < n_leaves; a build_split tree has more leaves — references — than triangles)
+                raise BvhError("self_pairs=True is not available on a build_split tree: it has more leaves than triangles; pass the mesh as `other` instead")
+            n = self.result.n_leaves
+        else:
+            if isinstance(other, np.ndarray):
+                if other.dtype == TRIANGLE:
+                    tri_format = TRI_PADDED64
+                else:
+                    f = np.asarray(other, dtype=np.float32)
+                    if f.ndim not in (2, 3) or f.size != f.shape[0] * 9:
+                        raise BvhError("other must have dtype TRIANGLE or shape (m, 9) / (m, 3, 3)")
+                    other, tri_format = f.reshape(-1, 9), TRI_PACKED36
+                n = other.shape[0]
+                own = other = ctx.upload(np.ascontiguousarray(other)) if n else None
+            elif other is None and vertices is None and indices is None:
+                raise BvhError("another mesh is required (only self_pairs=True goes without)")
+            elif n is None:
+                stride = {TRI_PADDED64: 64, TRI_PACKED36: 36}.get(tri_format)
+                n = other.nbytes // stride if isinstance(other, DeviceBuffer) and stride else (indices.nbytes // 12 if isinstance(indices, DeviceBuffer) else None)
+                if n is None:
+                    raise BvhError("n is required for a device mesh")
+            if n == 0:                                    # no queries: the empty answer, without a call
+                return np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=np.uint32)
+            qin = BuildInput(tri_format, 30, _ptr(other) if other is not None else None, _ptr(vertices) if vertices is not None else None,
+                             _ptr(indices) if indices is not None else None, n_vertices, 0)
+        tin = None
+        if tree_tris is None and tree_vertices is None and tree_indices is None and self._split is not None:
+            tree_tris, tree_tri_format = self._split["tris"], TRI_PADDED64      # (a build_split tree has no d_tris of its own)
+        if tree_tris is not None or tree_vertices is not None or tree_indices is not None:
+            tin = BuildInput(tree_tri_format, 30, _ptr(tree_tris) if tree_tris is not None else None, _ptr(tree_vertices) if tree_vertices is not None else None,
+                             _ptr(tree_indices) if tree_indices is not None else None, tree_n_vertices, 0)
+        mode = TRIS_SELF if self_pairs else TRIS_QUERY
+        what = f"{ALGO_NAMES[self.ALGO]}::intersect_tris"
+        offsets = ctx.alloc((n + 1) * 4)
+        prims = None
+        try:
+            cap = max(int(capacity) if capacity is not None else n, 1)
+            total = C.c_uint64()
+            for _ in range(2):
+                prims = ctx.alloc(cap * 4)
+                _check(lib().bvh_intersect_tris(ctx.handle, C.byref(self.result), C.byref(tin) if tin is not None else None,
+                                                C.byref(qin) if qin is not None else None, n, mode, offsets.ptr, prims.ptr, cap, C.byref(total)), what)
                 if total.value <= cap:
                     break
                 prims.free(); prims = None

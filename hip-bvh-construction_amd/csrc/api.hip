@@ -407,7 +407,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_point_query(); warm_winding(); warm_overlap(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -1083,6 +1083,75 @@ int bvh_overlap(bvh_ctx* c, const bvh_result* tree, const bvh_aabb* d_boxes, uin
         if (d_prims)
             launch_overlap_fill(s, (int)tree->layout, mode, d_boxes, n_boxes, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, d_prims, capacity, total,
                                 overflow + 1, c->parent);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
+    if (install.on) c->recorder.mark(s, nullptr);
+    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
+        u32* const rb = c->h_pinned + 8;
+        const int r = read_back(c, c->small + 60, 2, nullptr, 0, rb); if (r) return r;
+        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
+        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
+    }
+    return 0;
+}
+
+// ---- crossing triangle pairs (no counterpart in the reference) -------------------------------------------------------------------------------------
+// bvh_overlap's count -> scan -> fill sequence, overflow words, total word and read-back, with the query mesh's triangles in place of boxes; every argument is
+// checked before anything is enqueued, so an error writes nothing.  Neither output array may overlap the other or any array the call reads
+int bvh_intersect_tris(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_build_input* queries, uint32_t n_queries, int mode,
+                       uint32_t* d_offsets, uint32_t* d_prims, uint64_t capacity, uint64_t* total_out) {
+    if (!c || !tree || !d_offsets) return BVH_E_INVALID_ARG;
+    if (mode != BVH_TRIS_QUERY && mode != BVH_TRIS_SELF) return BVH_E_INVALID_ARG;
+    if ((mode == BVH_TRIS_SELF) != (queries == nullptr)) return BVH_E_INVALID_ARG;       // the other mesh, or none in self mode
+    const uint32_t n = tree->n_leaves;
+    if (n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1) return BVH_E_INVALID_ARG;
+    if (mode == BVH_TRIS_SELF && n_queries != n) return BVH_E_INVALID_ARG;
+    if (n_queries >= (1u << 30)) return BVH_E_INVALID_ARG;
+    bvh_build_input in; std::memset(&in, 0, sizeof in);
+    if (tris) { if (stage_extents_valid(tris)) return BVH_E_INVALID_ARG; in = *tris; }
+    else { if (!tree->d_tris) return BVH_E_INVALID_ARG; in.tri_format = BVH_TRI_PADDED64; in.d_tris = tree->d_tris; }
+    bvh_build_input qin = in;                                 // (self mode: the tree's own triangles)
+    if (queries) { if (stage_extents_valid(queries)) return BVH_E_INVALID_ARG; qin = *queries; }
+    if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
+    {   // the output arrays against each other and against everything the call reads (d_prims is never written past 2^32 - 1 words: a larger total skips the fill)
+        WindRange rg[9]; int k = 0;
+        auto add = [&](const void* p, uint64_t bytes) { rg[k].lo = (uintptr_t)p; rg[k].hi = rg[k].lo + bytes; ++k; };
+        auto add_mesh = [&](const bvh_build_input& m, uint32_t count) {
+            if (m.tri_format == BVH_TRI_INDEXED) { add(m.d_vertices, (uint64_t)m.n_vertices * 12u); add(m.d_indices, (uint64_t)count * 12u); }
+            else add(m.d_tris, (uint64_t)count * (m.tri_format == BVH_TRI_PACKED36 ? 36u : 64u));
+        };
+        add(tree->d_nodes, (uint64_t)(tree->layout == 0u ? 2ull * n - 1 : n - 1ull) * sizeof(bvh2_node));
+        if (tree->layout == 1u) add(tree->d_leaves, (uint64_t)n * sizeof(bvh_primref));
+        add_mesh(in, n);
+        if (queries) add_mesh(qin, n_queries);
+        const uint64_t off_bytes = ((uint64_t)n_queries + 1u) * sizeof(u32);
+        const uint64_t prim_bytes = d_prims ? (capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull) * sizeof(u32) : 0u;
+        if (wind_overlaps(rg, k, d_offsets, off_bytes) || wind_overlaps(rg, k, d_prims, prim_bytes)) return BVH_E_INVALID_ARG;
+        add(d_offsets, off_bytes);
+        if (wind_overlaps(rg + k - 1, 1, d_prims, prim_bytes)) return BVH_E_INVALID_ARG;
+    }
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    if (n_queries == 0) {                                     // d_offsets[0] = total = 0, nothing else
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
+        if (total_out) *total_out = 0;
+        return 0;
+    }
+    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
+    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    query_plan(c, tree, s);
+    u32* const overflow = c->small + 58;                      // bvh_overlap's words: [0] count pass, [1] fill pass (calls on one stream are ordered)
+    u64* const total = reinterpret_cast<u64*>(c->small + 60);
+    const TrisMesh tm{ (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices };
+    const TrisMesh qm{ (int)qin.tri_format, qin.d_tris, qin.d_vertices, qin.d_indices, qin.n_vertices };
+    hipError_t e = hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s);
+    if (e == hipSuccess) {
+        launch_tris_count(s, (int)tree->layout, mode, tm, qm, n_queries, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, overflow, c->parent,
+                          c->overlap_sums, total);
+        if (d_prims)
+            launch_tris_fill(s, (int)tree->layout, mode, tm, qm, n_queries, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, d_prims, capacity, total,
+                             overflow + 1, c->parent);
         e = hipGetLastError();
     }
     if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }

@@ -252,6 +252,22 @@ public:
         check(bvh_overlap(context.handle(), &m_result, d_boxes, n, static_cast<int>(mode), d_offsets, d_prims, capacity, nullptr), "overlap");
     }
 
+    // beyond the reference (bvh_intersect_tris): which of this tree's triangles each of the n triangles of `queries` (device pointers, any bvh_tri_format)
+    // properly crosses, as offsets + primitive indices; against the same tree and triangles as intersect.  BVH_TRIS_SELF: queries nullptr, n = the tree's own
+    // triangle count, every crossing pair once — only on a tree with one leaf per triangle (not on a tree over split references: the call reads triangle i for
+    // every i < n_leaves).  d_prims NULL: count only.  Returns the total (the call waits for it)
+    u64 intersectTris(Context& context, const bvh_build_input* queries, u32 n, bvh_tris_mode mode, u32* d_offsets, u32* d_prims, u64 capacity) {
+        uint64_t total = 0;
+        check(bvh_intersect_tris(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, queries, n, static_cast<int>(mode), d_offsets,
+                                 d_prims, capacity, &total), "intersectTris");
+        return total;
+    }
+    // the asynchronous form: no read-back, the fill decides on the device whether the capacity suffices
+    void intersectTrisAsync(Context& context, const bvh_build_input* queries, u32 n, bvh_tris_mode mode, u32* d_offsets, u32* d_prims, u64 capacity) {
+        check(bvh_intersect_tris(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, queries, n, static_cast<int>(mode), d_offsets,
+                                 d_prims, capacity, nullptr), "intersectTris");
+    }
+
     // beyond the reference (bvh_intersect_all): every accepted hit along each ray, as offsets + bvh_hit records (ascending (t, prim) per ray with
     // BVH_HITS_SORTED in flags); against the same tree and triangles as intersect.  d_hits NULL: count only.  Returns the total (the call waits for it)
     u64 intersectAll(Context& context, const bvh_ray* d_rays, u32 n, u32 flags, u32* d_offsets, bvh_hit* d_hits, u64 capacity) {

@@ -543,6 +543,71 @@ int  bvh_overlap(bvh_ctx* ctx, const bvh_result* tree, const bvh_aabb* d_boxes, 
                  uint32_t* d_offsets /* u32[n_boxes + 1], device */, uint32_t* d_prims /* u32[capacity], device, or NULL: count only */,
                  uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
 
+/* ---- crossing triangle pairs (no counterpart in the reference) ---------------------------------------------------------------------------
+ * Which triangles of the tree does each triangle of another mesh cut — or, with BVH_TRIS_SELF, which triangles of the tree's own mesh cut each other?  Contact
+ * detection, self-intersection checks before meshing or booleans, mesh validation before a winding-number field.  bvh_overlap's broad phase and the exact narrow
+ * phase in one walk: no pair list goes through memory.
+ * tree, tris: as for bvh_intersect (tris NULL: tree->d_tris is Triangle[n_leaves]); nothing in the tree is written.  queries: the other mesh's n_queries
+ * triangles, device pointers, in any bvh_tri_format, independent of tris' (morton_bits is ignored); NULL with BVH_TRIS_SELF.
+ * The predicate.  All arithmetic is IEEE f64 on the f32 coordinates widened exactly, without contraction or reassociation.
+ *   orient(a, b, c, d), with ad = a - d, bd = b - d, cd = c - d:
+ *     ad.x * (bd.y * cd.z - bd.z * cd.y)  +  ad.y * (bd.z * cd.x - bd.x * cd.z)  +  ad.z * (bd.x * cd.y - bd.y * cd.x),   the three terms summed left to right.
+ *   edge_crosses(p, q; a, b, c), with sp = orient(a, b, c, p) and sq = orient(a, b, c, q), is true iff both
+ *     (sp > 0 && sq < 0) || (sp < 0 && sq > 0), and
+ *     orient(p, q, a, b), orient(p, q, b, c) and orient(p, q, c, a) are all > 0 or all < 0.
+ *   proper(T) is true iff none of T's nine coordinates is a NaN and, with u = v2 - v1, w = v3 - v1, one of u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z,
+ *     u.x * w.y - u.y * w.x is > 0 or < 0 (T has an area).
+ *   crosses(X, Y) is true iff X and Y are proper and one of the 3 edges of X, taken as (v1, v2), (v2, v3), (v3, v1), crosses Y = (v1, v2, v3), or one of Y's
+ *   crosses X.  Each plane side orient(a, b, c, p) is computed once per vertex with the arguments in exactly this order.
+ * (The determinants alone would report an edge of a zero-area triangle, or an edge between the two clean vertices of a triangle whose third holds a NaN, that
+ * passes through the other triangle's interior: such an edge is still a segment.  proper() is what keeps those two kinds out.)
+ * The comparisons are strict, a zero row gives an exact 0 and a NaN compares false; so
+ *   - only PROPER crossings are reported: an edge of one triangle passes through the interior of the other;
+ *   - touching is not a crossing: a vertex or an edge lying in the other's plane or on its boundary;
+ *   - coplanar overlap is not a crossing;
+ *   - identical triangles, zero-area triangles and triangles with a NaN are not a crossing;
+ *   - two triangles that share a vertex bitwise are reported only when an edge that does not contain the shared vertex crosses the other's interior;
+ *   - two triangles that share an edge are never reported;
+ *   - so a closed manifold mesh has an empty self set, without any adjacency test or index comparison, in all three triangle formats.
+ * tests/test_intersect_tris.py restates the predicate in numpy f64 (bit for bit) and in exact rational arithmetic; on this project's meshes and on triangles
+ * built to lie within an f32 ulp of touching the two agree on every pair.
+ * Answer: the pair (query triangle i, tree primitive j) is reported iff box_overlap(B(i), leafbox(j)) — bvh_overlap's test; B(i) is stage E's box of query
+ * triangle i (bvh_stage_extents_ex's expression, clamps against the reset box included), leafbox(j) the leaf record's box as bvh_overlap reads it — and
+ * crosses(query_i, tri_j).  Compressed-row form, as bvh_overlap's: d_prims[d_offsets[i] .. d_offsets[i+1]) holds the tree primitives that query triangle i
+ * crosses, i the query mesh's own triangle index; d_offsets[0] = 0, d_offsets[n_queries] = the total.  The order inside a slice is unspecified, but the same call
+ * on the same arrays gives the same bytes.  The set does not depend on the builder, the layout or the scheduler.
+ * Completeness condition: (1) every internal box contains its children's boxes — all of this library's trees satisfy that; (2) each leaf box is stage E's box
+ * of the triangle passed for it — that holds for a build, and for a refit with the same triangles that are passed to the query.  Two triangles that cross share
+ * a point, so their stage-E boxes overlap, and under (1) and (2) the walk reaches the pair.  On other arrays every reported pair still satisfies both tests,
+ * but pairs may be missing.  Arrays that are not a tree end in finite time with unspecified answers (d_prims is never written outside query i's slice).  A
+ * child or primitive index out of range is never followed or reported; a vertex index out of range reads vertex 0, as in bvh_build_ex.  On a tree relabelled by
+ * bvh_remap_leaves (BVH_TRIS_QUERY only, see below) a pair can appear once per reference reached; this is not deduplicated.
+ * BVH_TRIS_SELF: the queries are the tree's own triangles (tris), n_queries must equal n_leaves, and only j > i is reported: each unordered pair once, as j in
+ * i's slice, and no triangle with itself.  The call reads triangle i of tris for EVERY i < n_leaves, so tris must hold n_leaves triangles (an indexed tris:
+ * n_leaves index triples).  That is a requirement on the caller which the call cannot check: BVH_TRIS_SELF is NOT usable on a tree with more leaves than
+ * triangles — a tree over bvh_split_refs references relabelled by bvh_remap_leaves — where it would read past the end of the triangle array.  For such a tree
+ * pass the mesh itself as queries with BVH_TRIS_QUERY (the Python binding refuses self_pairs on a build_split tree).
+ * Passes, capacity, total_out, saturation and BVH_E_TOO_LARGE: bvh_overlap's, word for word.  The call always counts, then scans the counts into d_offsets, and
+ * keeps the 64-bit total in a device word.  It fills d_prims iff d_prims != NULL, total <= capacity and total < 2^32; that decision is made ON THE DEVICE (the
+ * fill launch reads the total word and returns at once), so the call stays asynchronous on the ctx's stream.  If the fill is skipped d_prims is not touched
+ * and d_offsets is still complete.  With total_out != NULL the call blocks on an 8-byte read-back into pinned words and stores the total.  A total of 2^32 or
+ * more saturates d_offsets at 0xFFFFFFFF; if total_out was given the call then returns BVH_E_TOO_LARGE (with *total_out set).
+ * There is no depth limit: a query whose short stack would overflow is finished by a stackless pass through bvh_refit's parent plan, cached for the ctx's own
+ * tree as for bvh_overlap and made per call for caller-owned arrays.  Count and fill agree on every query's set whichever pass served it.
+ * Errors (nothing is written or enqueued, BVH_E_INVALID_ARG): NULL ctx / tree / d_offsets, n_leaves < 2, layout not 0 or 1, NULL d_nodes, layout 1 with NULL
+ * d_leaves, root not an internal node, no triangles (tris NULL and tree->d_tris NULL), a format error in tris or queries (an unknown tri_format, a NULL or — for
+ * PACKED36 — misaligned d_tris, INDEXED with a NULL vertex or index pointer or n_vertices == 0), mode not 0 or 1, NULL queries without BVH_TRIS_SELF, queries
+ * given with BVH_TRIS_SELF, BVH_TRIS_SELF with n_queries != n_leaves, n_queries >= 2^30, n_leaves larger than the ctx's capacity (the parent plan lives in the
+ * arena; call bvh_ctx_reserve first), d_offsets or d_prims (capacity words) overlapping each other or a node, leaf, triangle, vertex or index array of the call.
+ * n_queries == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.
+ * bvh_ctx_kernel_times reports k_tris_count, k_tris_deep (after each pass), k_overlap_scan (the scan is bvh_overlap's), k_tris_fill and, when the plan is
+ * made, k_refit_plan. */
+typedef enum { BVH_TRIS_QUERY = 0, BVH_TRIS_SELF = 1 } bvh_tris_mode;
+int  bvh_intersect_tris(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
+                        const bvh_build_input* queries /* the other mesh, device; any bvh_tri_format, independent of tris'; NULL with BVH_TRIS_SELF */,
+                        uint32_t n_queries, int mode /* bvh_tris_mode */, uint32_t* d_offsets /* u32[n_queries + 1], device */,
+                        uint32_t* d_prims /* u32[capacity], device, or NULL: count only */, uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+
 /* ---- early split clipping (Utility::doEarlySplitClipping, src/Utility.cpp:456-538: the PrimRef[] front end of the reference's LBVH builders) -------------
  * Large triangles become several REFERENCES {box, triangle index}: a box whose surface area exceeds sa_max is halved at its centre on its longest axis until
  * every piece is small enough, and the tree is then built over the pieces (bvh_build_boxes), so a wall that spans the scene no longer owns a scene-sized leaf.
@@ -588,6 +653,9 @@ int  bvh_overlap(bvh_ctx* ctx, const bvh_result* tree, const bvh_aabb* d_boxes, 
  *   bvh_intersect_all, bvh_knn, bvh_radius_search, bvh_overlap: valid, but they report a triangle ONCE PER REFERENCE REACHED (duplicates within a slice; a
  *     bvh_knn list can fill with one triangle's references).  BVH_OVERLAP_SELF compares reference positions before and triangle indices after a relabelling;
  *     run it before.
+ *   bvh_intersect_tris: BVH_TRIS_QUERY is valid after the relabelling, with the original triangles as `tris`, and likewise reports a triangle once per
+ *     reference reached; deduplicated, the set equals the unsplit tree's (a crossing point lies in one of the references, which tile the triangle's box).
+ *     BVH_TRIS_SELF is NOT valid on such a tree, before or after: it reads triangle i of `tris` for every i < n_leaves, and there are fewer triangles.
  *   bvh_sah_cost needs nothing but the tree and may run at any time; bvh_optimize likewise (it moves no leaf).  bvh_bvh4_cost indexes d_prim_aabbs by the
  *     leaves' primitive index: run it BEFORE the relabelling, while d_prim_aabbs (the reference boxes) still matches the leaves.
  *   bvh_refit, bvh_refit_ex, bvh_refit_subset: NOT applicable to a tree over references, relabelled or not — they would read Triangle[n_leaves] and give leaf j
