@@ -317,6 +317,116 @@ class DeviceBuffer:
             pass
 
 
+def _build_input(tri_format, tris, vertices, indices, n_vertices, morton_bits: int = 30) -> BuildInput:
+    return BuildInput(tri_format, morton_bits, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
+                      _ptr(indices) if indices is not None else None, n_vertices, 0)
+
+
+def _tri_input(tris, vertices, indices, n_vertices, tri_format):
+    """the BuildInput of the device triangles a query names, or None where it names none (the call then reads the tree's own d_tris)"""
+    if tris is None and vertices is None and indices is None:
+        return None
+    return _build_input(tri_format, tris, vertices, indices, n_vertices)
+
+
+def _ref(struct):
+    return C.byref(struct) if struct is not None else None
+
+
+def _device_count(buf, n, itemsize, name, what):
+    """the record count of a device query array: given, or a DeviceBuffer's size"""
+    if n is None and isinstance(buf, DeviceBuffer):
+        n = buf.nbytes // itemsize
+    if n is None:
+        raise BvhError(f"{name} is required for device {what}")
+    return n
+
+
+def _uploaded(ctx, host):
+    """a host query array -> (device buffer or None for no queries, n, the same buffer: the caller frees it after the call)"""
+    n = host.shape[0]
+    own = ctx.upload(np.ascontiguousarray(host)) if n else None
+    return own, n, own
+
+
+def _as_rays(ctx, rays, n, name="n_rays"):
+    """a host RAY array or device rays with their count -> (device pointer or buffer, n, the buffer uploaded for the call or None)"""
+    if isinstance(rays, np.ndarray):
+        if rays.dtype != RAY:
+            raise BvhError("rays must have dtype RAY (32-byte records)")
+        return _uploaded(ctx, rays)
+    return rays, _device_count(rays, n, RAY.itemsize, name, "rays"), None
+
+
+def _as_points(ctx, points, radius, n):
+    """a host POINT_QUERY array, a host (n, 3) float array whose radius is ``radius`` (None: +inf) or device POINT_QUERY records with their count ->
+    (device pointer or buffer, n, the buffer uploaded for the call or None)"""
+    if isinstance(points, np.ndarray):
+        if points.dtype != POINT_QUERY:
+            xyz = np.asarray(points, dtype=np.float32)
+            if xyz.ndim != 2 or xyz.shape[1] != 3:
+                raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
+            points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
+            points["point"] = xyz
+            points["radius"] = np.float32(np.inf) if radius is None else np.asarray(radius, dtype=np.float32)
+        elif radius is not None:
+            raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
+        return _uploaded(ctx, points)
+    return points, _device_count(points, n, POINT_QUERY.itemsize, "n_points", "points"), None
+
+
+def _as_boxes(ctx, boxes, n, name="n", rows_only=True):
+    """a host AABB array, host floats ((m, 6) with ``rows_only``, as the builders' overlap takes them; any shape of 6 floats per box without, as Scene.overlap
+    does) or device bvh_aabb records with their count -> (device pointer or buffer, n, the buffer uploaded for the call or None)"""
+    if isinstance(boxes, np.ndarray):
+        if boxes.dtype != AABB:
+            f = np.ascontiguousarray(boxes, dtype=np.float32)
+            if rows_only:
+                if f.ndim != 2 or f.shape[1] != 6:
+                    raise BvhError("boxes must have dtype AABB or shape (m, 6)")
+            elif f.size % 6 or (f.ndim >= 2 and int(np.prod(f.shape[1:])) != 6):
+                raise BvhError("boxes must have dtype AABB or 6 floats per box")
+            boxes = f.reshape(-1, 6)
+        return _uploaded(ctx, boxes)
+    return boxes, _device_count(boxes, n, AABB.itemsize, name, "boxes"), None
+
+
+def _count_fill(ctx, call, n, rec_dtype, count_only, capacity, what, own=None):
+    """The host side of a count -> scan -> fill call over n queries.  ``call(offsets_ptr, records_ptr, capacity, total_ref)`` makes the C call and returns its
+    code.  ``count_only`` or no ``capacity``: a count-only call first; then up to two calls with a record buffer, the second with the total the first
+    reported when the capacity was too small.  Returns offsets u32[n + 1] (``count_only``) or (offsets, records rec_dtype[total]); frees its buffers and ``own``."""
+    offsets, out = ctx.alloc((n + 1) * 4), None
+    try:
+        total = C.c_uint64()
+        if count_only or capacity is None:
+            _check(call(offsets.ptr, None, 0, C.byref(total)), what)
+            if count_only:
+                return offsets.download(np.uint32, n + 1)
+            cap = total.value
+        else:
+            cap = int(capacity)
+        for _ in range(2):
+            out = ctx.alloc(max(cap, 1) * np.dtype(rec_dtype).itemsize)
+            _check(call(offsets.ptr, out.ptr, cap, C.byref(total)), what)
+            if total.value <= cap:
+                break
+            out.free(); out = None
+            cap = total.value
+        return offsets.download(np.uint32, n + 1), out.download(rec_dtype, total.value)
+    finally:
+        offsets.free()
+        if out is not None:
+            out.free()
+        if own is not None:
+            own.free()
+
+
+def _no_queries(count_only, rec_dtype):
+    """the answer to no queries, given without a call"""
+    off = np.zeros(1, dtype=np.uint32)
+    return off if count_only else (off, np.zeros(0, dtype=rec_dtype))
+
+
 def many_layout(counts):
     """bvh_build_many's output layout: (out_off, node_off, total) for the meshes' triangle counts — mesh m's d_prim_aabbs / d_sorted_* slices start at
     out_off[m] (the exclusive scan of the counts), its 2*count-1 node records at record node_off[m] = 2*out_off[m] - m; total = the sum of the counts."""
@@ -605,8 +715,7 @@ class Context:
             tri_format = TRI_PADDED64
         elif n is None:
             raise BvhError("n is required for device inputs")
-        inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                         _ptr(indices) if indices is not None else None, n_vertices, 0)
+        inp = _build_input(tri_format, tris, vertices, indices, n_vertices)
         offsets = self.alloc((n + 1) * 4)
         boxes = prims = None
         done = False
@@ -652,8 +761,7 @@ class Context:
             if tri_format == TRI_INDEXED:
                 n_vertices = len(host["vertices"])
         ranges = many_check_ranges(ranges, n_tris, tri_format)
-        inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                         _ptr(indices) if indices is not None else None, n_vertices, 0)
+        inp = _build_input(tri_format, tris, vertices, indices, n_vertices)
         return inp, ranges, n_tris
 
     def build_many(self, meshes, algo: int = ALGO_TWOPASS, tri_format: int = TRI_PADDED64, vertices=None, indices=None, n_vertices: int = 0,
@@ -756,8 +864,7 @@ class _Builder:
         """bvh_build_ex: device inputs in any bvh_tri_format, 30- or 60-bit Morton codes."""
         self._ctx = context
         self._free_split()
-        inp = BuildInput(tri_format, morton_bits, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                         _ptr(indices) if indices is not None else None, n_vertices, 0)
+        inp = _build_input(tri_format, tris, vertices, indices, n_vertices, morton_bits)
         _check(lib().bvh_build_ex(context.handle, self.ALGO, C.byref(inp), n, C.byref(self.result), C.byref(self.timings)), f"{ALGO_NAMES[self.ALGO]}::build_ex")
         return self._publish()
 
@@ -864,8 +971,7 @@ class _Builder:
             raise BvhError("refit needs a built tree")
         if n is not None and n != self.result.n_leaves:
             raise BvhError(f"refit with {n} triangles of a tree over {self.result.n_leaves}")
-        inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                         _ptr(indices) if indices is not None else None, n_vertices, 0)
+        inp = _build_input(tri_format, tris, vertices, indices, n_vertices)
         _check(lib().bvh_refit_ex(self._ctx.handle, C.byref(self.result), C.byref(inp), C.byref(self.timings)), f"{ALGO_NAMES[self.ALGO]}::refit_ex")
         return self._publish()
 
@@ -890,8 +996,7 @@ class _Builder:
                 raise BvhError("n_dirty is required for device lists")
         inp = None
         if tris is not None or vertices is not None or indices is not None or tri_format != TRI_PADDED64:
-            inp = C.byref(BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                                     _ptr(indices) if indices is not None else None, n_vertices, 0))
+            inp = C.byref(_build_input(tri_format, tris, vertices, indices, n_vertices))
         try:
             _check(lib().bvh_refit_subset(ctx.handle, C.byref(self.result), inp, _ptr(prims) or None, int(n_dirty), C.byref(self.timings)),
                    f"{ALGO_NAMES[self.ALGO]}::refit_subset")
@@ -917,32 +1022,18 @@ class _Builder:
             raise BvhError("intersect needs a built tree")
         ctx = self._ctx
         q = _QUERY_IDS[query] if isinstance(query, str) else int(query)
-        own = None
-        if isinstance(rays, np.ndarray):
-            if rays.dtype != RAY:
-                raise BvhError("rays must have dtype RAY (32-byte records)")
-            n_rays = rays.shape[0]
-            own = rays = ctx.upload(np.ascontiguousarray(rays)) if n_rays else None
-        elif n_rays is None:
-            n_rays = rays.nbytes // RAY.itemsize if isinstance(rays, DeviceBuffer) else None
-            if n_rays is None:
-                raise BvhError("n_rays is required for device rays")
-        inp = None
-        if tris is None and vertices is None and indices is None and self._split is not None:
-            tris, tri_format = self._split["tris"], TRI_PADDED64      # (a build_split tree has no d_tris of its own)
-        if tris is not None or vertices is not None or indices is not None:
-            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                             _ptr(indices) if indices is not None else None, n_vertices, 0)
+        rays, n_rays, own = _as_rays(ctx, rays, n_rays)
+        tris, tri_format = self._own_tris(tris, vertices, indices, tri_format)
+        inp = _tri_input(tris, vertices, indices, n_vertices, tri_format)
         hits = ctx.alloc(max(n_rays, 1) * HIT.itemsize)
         try:
-            _check(lib().bvh_intersect(ctx.handle, C.byref(self.result), C.byref(inp) if inp is not None else None, _ptr(rays) if rays is not None else None,
-                                       n_rays, hits.ptr, q), f"{ALGO_NAMES[self.ALGO]}::intersect")
+            _check(lib().bvh_intersect(ctx.handle, C.byref(self.result), _ref(inp), _ptr(rays) if rays is not None else None, n_rays, hits.ptr, q),
+                   f"{ALGO_NAMES[self.ALGO]}::intersect")
             return hits.download(HIT, n_rays)
         finally:
             hits.free()
             if own is not None:
                 own.free()
-
     def closest_point(self, points, radius=None, query="closest", tris=None, vertices=None, indices=None, n_vertices: int = 0,
                       tri_format: int = TRI_PADDED64, n_points: int | None = None) -> np.ndarray:
         """bvh_closest_point on this builder's tree: ``points`` a host POINT_QUERY array, a host (n, 3) float array whose radius is ``radius`` (None: +inf),
@@ -952,38 +1043,23 @@ class _Builder:
             raise BvhError("closest_point needs a built tree")
         ctx = self._ctx
         q = _QUERY_IDS[query] if isinstance(query, str) else int(query)
-        own = None
-        if isinstance(points, np.ndarray):
-            if points.dtype != POINT_QUERY:
-                xyz = np.asarray(points, dtype=np.float32)
-                if xyz.ndim != 2 or xyz.shape[1] != 3:
-                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
-                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
-                points["point"] = xyz
-                points["radius"] = np.float32(np.inf) if radius is None else np.float32(radius)
-            elif radius is not None:
-                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
-            n_points = points.shape[0]
-            own = points = ctx.upload(np.ascontiguousarray(points)) if n_points else None
-        elif n_points is None:
-            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
-            if n_points is None:
-                raise BvhError("n_points is required for device points")
-        inp = None
-        if tris is None and vertices is None and indices is None and self._split is not None:
-            tris, tri_format = self._split["tris"], TRI_PADDED64      # (a build_split tree has no d_tris of its own)
-        if tris is not None or vertices is not None or indices is not None:
-            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                             _ptr(indices) if indices is not None else None, n_vertices, 0)
+        points, n_points, own = _as_points(ctx, points, radius, n_points)
+        tris, tri_format = self._own_tris(tris, vertices, indices, tri_format)
+        inp = _tri_input(tris, vertices, indices, n_vertices, tri_format)
         hits = ctx.alloc(max(n_points, 1) * POINT_HIT.itemsize)
         try:
-            _check(lib().bvh_closest_point(ctx.handle, C.byref(self.result), C.byref(inp) if inp is not None else None,
-                                           _ptr(points) if points is not None else None, n_points, hits.ptr, q), f"{ALGO_NAMES[self.ALGO]}::closest_point")
+            _check(lib().bvh_closest_point(ctx.handle, C.byref(self.result), _ref(inp), _ptr(points) if points is not None else None, n_points, hits.ptr, q),
+                   f"{ALGO_NAMES[self.ALGO]}::closest_point")
             return hits.download(POINT_HIT, n_points)
         finally:
             hits.free()
             if own is not None:
                 own.free()
+    def _own_tris(self, tris, vertices, indices, tri_format):
+        """(tris, tri_format) of a call that names no triangles on a build_split tree, which has no d_tris of its own: the triangles the builder kept"""
+        if tris is None and vertices is None and indices is None and self._split is not None:
+            return self._split["tris"], TRI_PADDED64
+        return tris, tri_format
 
     def _free_winding(self) -> None:
         if self._winding is not None:
@@ -992,14 +1068,9 @@ class _Builder:
 
     def _winding_input(self, tris, vertices, indices, n_vertices, tri_format):
         """(key, BuildInput or None) of the triangles a winding call names, as intersect's"""
-        if tris is None and vertices is None and indices is None and self._split is not None:
-            tris, tri_format = self._split["tris"], TRI_PADDED64      # (a build_split tree has no d_tris of its own)
-        if tris is None and vertices is None and indices is None:
-            return None, None
-        key = (int(tri_format), _ptr(tris), _ptr(vertices), _ptr(indices), int(n_vertices))
-        return key, BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                               _ptr(indices) if indices is not None else None, n_vertices, 0)
-
+        tris, tri_format = self._own_tris(tris, vertices, indices, tri_format)
+        inp = _tri_input(tris, vertices, indices, n_vertices, tri_format)
+        return (None if inp is None else (int(tri_format), _ptr(tris), _ptr(vertices), _ptr(indices), int(n_vertices))), inp
     def winding_prepare(self, tris=None, vertices=None, indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64) -> DeviceBuffer:
         """bvh_winding_prepare on this builder's tree: the per-node moments (WINDING_MOMENT[n_leaves - 1]) in a device buffer the builder keeps and returns.
         Triangles as for intersect.  build* / refit* / optimize / remap_leaves free the buffer: the moments of the old tree are stale."""
@@ -1009,7 +1080,7 @@ class _Builder:
         self._free_winding()
         buf = self._ctx.alloc((self.result.n_leaves - 1) * WINDING_MOMENT.itemsize)
         try:
-            _check(lib().bvh_winding_prepare(self._ctx.handle, C.byref(self.result), C.byref(inp) if inp is not None else None, buf.ptr),
+            _check(lib().bvh_winding_prepare(self._ctx.handle, C.byref(self.result), _ref(inp), buf.ptr),
                    f"{ALGO_NAMES[self.ALGO]}::winding_prepare")
         except Exception:
             buf.free()
@@ -1028,32 +1099,18 @@ class _Builder:
         key, inp = self._winding_input(tris, vertices, indices, n_vertices, tri_format)
         if self._winding is None or self._winding[0] != key:
             self.winding_prepare(tris, vertices, indices, n_vertices, tri_format)
-        own = None
-        if isinstance(points, np.ndarray):
-            if points.dtype != POINT_QUERY:
-                xyz = np.asarray(points, dtype=np.float32)
-                if xyz.ndim != 2 or xyz.shape[1] != 3:
-                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
-                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
-                points["point"] = xyz
-            n_points = points.shape[0]
-            own = points = ctx.upload(np.ascontiguousarray(points)) if n_points else None
-        elif n_points is None:
-            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
-            if n_points is None:
-                raise BvhError("n_points is required for device points")
+        points, n_points, own = _as_points(ctx, points, None, n_points)      # (the radius is not read)
         if n_points == 0:
             return np.empty(0, dtype=np.float32)
         w = ctx.alloc(n_points * 4)
         try:
-            _check(lib().bvh_winding_number(ctx.handle, C.byref(self.result), C.byref(inp) if inp is not None else None, self._winding[1].ptr, _ptr(points),
-                                            n_points, float(beta), w.ptr), f"{ALGO_NAMES[self.ALGO]}::winding_number")
+            _check(lib().bvh_winding_number(ctx.handle, C.byref(self.result), _ref(inp), self._winding[1].ptr, _ptr(points), n_points, float(beta), w.ptr),
+                   f"{ALGO_NAMES[self.ALGO]}::winding_number")
             return w.download(np.float32, n_points)
         finally:
             w.free()
             if own is not None:
                 own.free()
-
     def signed_distance(self, points, beta: float = 2.0, tris=None, vertices=None, indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64):
         """-> (sd f32[n], hits POINT_HIT[n]): closest_point's distance sqrt(dist2) (unbounded radius), negated where winding_number > 0.5 (inside).  ``points``: a
         host (n, 3) float array or POINT_QUERY records (their radius is replaced by +inf).  Plain composition of the two calls."""
@@ -1078,38 +1135,18 @@ class _Builder:
         k = int(k)
         if not 1 <= k <= KNN_MAX_K:
             raise BvhError(f"k must be 1 .. {KNN_MAX_K}")
-        own = None
-        if isinstance(points, np.ndarray):
-            if points.dtype != POINT_QUERY:
-                xyz = np.asarray(points, dtype=np.float32)
-                if xyz.ndim != 2 or xyz.shape[1] != 3:
-                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
-                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
-                points["point"] = xyz
-                points["radius"] = np.float32(np.inf) if radius is None else np.float32(radius)
-            elif radius is not None:
-                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
-            n_points = points.shape[0]
-            own = points = ctx.upload(np.ascontiguousarray(points)) if n_points else None
-        elif n_points is None:
-            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
-            if n_points is None:
-                raise BvhError("n_points is required for device points")
-        inp = None
-        if tris is not None or vertices is not None or indices is not None:
-            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                             _ptr(indices) if indices is not None else None, n_vertices, 0)
+        points, n_points, own = _as_points(ctx, points, radius, n_points)
+        inp = _tri_input(tris, vertices, indices, n_vertices, tri_format)
         hits = ctx.alloc(max(n_points * k, 1) * KNN_HIT.itemsize)
         counts = ctx.alloc(max(n_points, 1) * 4)
         try:
-            _check(lib().bvh_knn(ctx.handle, C.byref(self.result), C.byref(inp) if inp is not None else None,
-                                 _ptr(points) if points is not None else None, n_points, k, hits.ptr, counts.ptr), f"{ALGO_NAMES[self.ALGO]}::knn")
+            _check(lib().bvh_knn(ctx.handle, C.byref(self.result), _ref(inp), _ptr(points) if points is not None else None, n_points, k, hits.ptr, counts.ptr),
+                   f"{ALGO_NAMES[self.ALGO]}::knn")
             return hits.download(KNN_HIT, n_points * k).reshape(n_points, k), counts.download(np.uint32, n_points)
         finally:
             hits.free(); counts.free()
             if own is not None:
                 own.free()
-
     def overlap(self, boxes=None, self_pairs: bool = False, capacity: int | None = None, n: int | None = None):
         """bvh_overlap on this builder's tree: which primitives' boxes each query box touches.  ``boxes`` a host AABB array, a host (m, 6) float array
         (min xyz, max xyz), or a device buffer of bvh_aabb records (DeviceBuffer / int address, with ``n``).  ``self_pairs=True`` is BVH_OVERLAP_SELF: ``boxes``
@@ -1124,42 +1161,14 @@ class _Builder:
             if not self_pairs or not self.result.d_prim_aabbs:
                 raise BvhError("boxes are required (only self_pairs=True defaults them to the tree's own primitive boxes)")
             boxes, n = self.result.d_prim_aabbs, self.result.n_leaves
-        elif isinstance(boxes, np.ndarray):
-            if boxes.dtype != AABB:
-                f = np.asarray(boxes, dtype=np.float32)
-                if f.ndim != 2 or f.shape[1] != 6:
-                    raise BvhError("boxes must have dtype AABB or shape (m, 6)")
-                boxes = np.ascontiguousarray(f).view(AABB).reshape(-1)
-            n = boxes.shape[0]
-            own = boxes = ctx.upload(np.ascontiguousarray(boxes)) if n else None
-        elif n is None:
-            n = boxes.nbytes // AABB.itemsize if isinstance(boxes, DeviceBuffer) else None
-            if n is None:
-                raise BvhError("n is required for device boxes")
+        else:
+            boxes, n, own = _as_boxes(ctx, boxes, n)
         mode = OVERLAP_SELF if self_pairs else OVERLAP_BOXES
-        what = f"{ALGO_NAMES[self.ALGO]}::overlap"
         if n == 0 and not self_pairs:                     # no queries: the empty answer, without a call
-            return np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=np.uint32)
-        offsets = ctx.alloc((n + 1) * 4)
-        prims = None
-        try:
-            cap = max(int(capacity) if capacity is not None else 8 * n, 1)
-            total = C.c_uint64()
-            for _ in range(2):
-                prims = ctx.alloc(cap * 4)
-                _check(lib().bvh_overlap(ctx.handle, C.byref(self.result), _ptr(boxes), n, mode, offsets.ptr, prims.ptr, cap, C.byref(total)), what)
-                if total.value <= cap:
-                    break
-                prims.free(); prims = None
-                cap = total.value
-            return offsets.download(np.uint32, n + 1), prims.download(np.uint32, total.value)
-        finally:
-            offsets.free()
-            if prims is not None:
-                prims.free()
-            if own is not None:
-                own.free()
-
+            return _no_queries(False, np.uint32)
+        res = C.byref(self.result)
+        return _count_fill(ctx, lambda off, out, cap, tot: lib().bvh_overlap(ctx.handle, res, _ptr(boxes), n, mode, off, out, cap, tot), n, np.uint32, False,
+                           max(int(capacity) if capacity is not None else 8 * n, 1), f"{ALGO_NAMES[self.ALGO]}::overlap", own)
     def intersect_tris(self, other=None, self_pairs: bool = False, capacity: int | None = None, tri_format: int = TRI_PADDED64, vertices=None, indices=None,
                        n_vertices: int = 0, n: int | None = None, tree_tris=None, tree_vertices=None, tree_indices=None, tree_n_vertices: int = 0,
                        tree_tri_format: int = TRI_PADDED64):
@@ -1192,8 +1201,7 @@ class _Builder:
                     if f.ndim not in (2, 3) or f.size != f.shape[0] * 9:
                         raise BvhError("other must have dtype TRIANGLE or shape (m, 9) / (m, 3, 3)")
                     other, tri_format = f.reshape(-1, 9), TRI_PACKED36
-                n = other.shape[0]
-                own = other = ctx.upload(np.ascontiguousarray(other)) if n else None
+                other, n, own = _uploaded(ctx, other)
             elif other is None and vertices is None and indices is None:
                 raise BvhError("another mesh is required (only self_pairs=True goes without)")
             elif n is None:
@@ -1202,38 +1210,14 @@ class _Builder:
                 if n is None:
                     raise BvhError("n is required for a device mesh")
             if n == 0:                                    # no queries: the empty answer, without a call
-                return np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=np.uint32)
-            qin = BuildInput(tri_format, 30, _ptr(other) if other is not None else None, _ptr(vertices) if vertices is not None else None,
-                             _ptr(indices) if indices is not None else None, n_vertices, 0)
-        tin = None
-        if tree_tris is None and tree_vertices is None and tree_indices is None and self._split is not None:
-            tree_tris, tree_tri_format = self._split["tris"], TRI_PADDED64      # (a build_split tree has no d_tris of its own)
-        if tree_tris is not None or tree_vertices is not None or tree_indices is not None:
-            tin = BuildInput(tree_tri_format, 30, _ptr(tree_tris) if tree_tris is not None else None, _ptr(tree_vertices) if tree_vertices is not None else None,
-                             _ptr(tree_indices) if tree_indices is not None else None, tree_n_vertices, 0)
+                return _no_queries(False, np.uint32)
+            qin = _build_input(tri_format, other, vertices, indices, n_vertices)
+        tree_tris, tree_tri_format = self._own_tris(tree_tris, tree_vertices, tree_indices, tree_tri_format)
+        tin = _tri_input(tree_tris, tree_vertices, tree_indices, tree_n_vertices, tree_tri_format)
         mode = TRIS_SELF if self_pairs else TRIS_QUERY
-        what = f"{ALGO_NAMES[self.ALGO]}::intersect_tris"
-        offsets = ctx.alloc((n + 1) * 4)
-        prims = None
-        try:
-            cap = max(int(capacity) if capacity is not None else n, 1)
-            total = C.c_uint64()
-            for _ in range(2):
-                prims = ctx.alloc(cap * 4)
-                _check(lib().bvh_intersect_tris(ctx.handle, C.byref(self.result), C.byref(tin) if tin is not None else None,
-                                                C.byref(qin) if qin is not None else None, n, mode, offsets.ptr, prims.ptr, cap, C.byref(total)), what)
-                if total.value <= cap:
-                    break
-                prims.free(); prims = None
-                cap = total.value
-            return offsets.download(np.uint32, n + 1), prims.download(np.uint32, total.value)
-        finally:
-            offsets.free()
-            if prims is not None:
-                prims.free()
-            if own is not None:
-                own.free()
-
+        res = C.byref(self.result)
+        return _count_fill(ctx, lambda off, out, cap, tot: lib().bvh_intersect_tris(ctx.handle, res, _ref(tin), _ref(qin), n, mode, off, out, cap, tot), n,
+                           np.uint32, False, max(int(capacity) if capacity is not None else n, 1), f"{ALGO_NAMES[self.ALGO]}::intersect_tris", own)
     def intersect_all(self, rays, sorted: bool = True, count_only: bool = False, capacity: int | None = None, tris=None, vertices=None, indices=None,
                       n_vertices: int = 0, tri_format: int = TRI_PADDED64, n: int | None = None):
         """bvh_intersect_all on this builder's tree: every accepted hit along each ray.  ``rays`` a host RAY array or a device buffer (DeviceBuffer / int
@@ -1244,52 +1228,13 @@ class _Builder:
         if self._ctx is None:
             raise BvhError("intersect_all needs a built tree")
         ctx = self._ctx
-        own = None
-        if isinstance(rays, np.ndarray):
-            if rays.dtype != RAY:
-                raise BvhError("rays must have dtype RAY (32-byte records)")
-            n = rays.shape[0]
-            own = rays = ctx.upload(np.ascontiguousarray(rays)) if n else None
-        elif n is None:
-            n = rays.nbytes // RAY.itemsize if isinstance(rays, DeviceBuffer) else None
-            if n is None:
-                raise BvhError("n is required for device rays")
+        rays, n, own = _as_rays(ctx, rays, n, "n")
         if n == 0:                                        # no rays: the empty answer, without a call
-            off = np.zeros(1, dtype=np.uint32)
-            return off if count_only else (off, np.zeros(0, dtype=HIT))
-        inp = None
-        if tris is not None or vertices is not None or indices is not None:
-            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                             _ptr(indices) if indices is not None else None, n_vertices, 0)
-        p_inp = C.byref(inp) if inp is not None else None
-        flags = HITS_SORTED if sorted else 0
-        what = f"{ALGO_NAMES[self.ALGO]}::intersect_all"
-        offsets = ctx.alloc((n + 1) * 4)
-        hits = None
-        try:
-            total = C.c_uint64()
-            if count_only or capacity is None:
-                _check(lib().bvh_intersect_all(ctx.handle, C.byref(self.result), p_inp, _ptr(rays), n, flags, offsets.ptr, None, 0, C.byref(total)), what)
-                if count_only:
-                    return offsets.download(np.uint32, n + 1)
-                cap = total.value
-            else:
-                cap = int(capacity)
-            for _ in range(2):
-                hits = ctx.alloc(max(cap, 1) * HIT.itemsize)
-                _check(lib().bvh_intersect_all(ctx.handle, C.byref(self.result), p_inp, _ptr(rays), n, flags, offsets.ptr, hits.ptr, cap, C.byref(total)), what)
-                if total.value <= cap:
-                    break
-                hits.free(); hits = None
-                cap = total.value
-            return offsets.download(np.uint32, n + 1), hits.download(HIT, total.value)
-        finally:
-            offsets.free()
-            if hits is not None:
-                hits.free()
-            if own is not None:
-                own.free()
-
+            return _no_queries(count_only, HIT)
+        inp = _tri_input(tris, vertices, indices, n_vertices, tri_format)
+        res, flags = C.byref(self.result), HITS_SORTED if sorted else 0
+        return _count_fill(ctx, lambda off, out, cap, tot: lib().bvh_intersect_all(ctx.handle, res, _ref(inp), _ptr(rays), n, flags, off, out, cap, tot), n,
+                           HIT, count_only, capacity, f"{ALGO_NAMES[self.ALGO]}::intersect_all", own)
     def radius_search(self, points, radius=None, sorted: bool = True, count_only: bool = False, capacity: int | None = None, tris=None, vertices=None,
                       indices=None, n_vertices: int = 0, tri_format: int = TRI_PADDED64, n_points: int | None = None):
         """bvh_radius_search on this builder's tree: every triangle within each query's radius.  ``points`` as for closest_point (a host POINT_QUERY array, a
@@ -1301,60 +1246,13 @@ class _Builder:
         if self._ctx is None:
             raise BvhError("radius_search needs a built tree")
         ctx = self._ctx
-        own = None
-        if isinstance(points, np.ndarray):
-            if points.dtype != POINT_QUERY:
-                xyz = np.asarray(points, dtype=np.float32)
-                if xyz.ndim != 2 or xyz.shape[1] != 3:
-                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
-                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
-                points["point"] = xyz
-                points["radius"] = np.float32(np.inf) if radius is None else np.asarray(radius, dtype=np.float32)
-            elif radius is not None:
-                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
-            n_points = points.shape[0]
-            own = points = ctx.upload(np.ascontiguousarray(points)) if n_points else None
-        elif n_points is None:
-            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
-            if n_points is None:
-                raise BvhError("n_points is required for device points")
-        n = n_points
+        points, n, own = _as_points(ctx, points, radius, n_points)
         if n == 0:                                        # no queries: the empty answer, without a call
-            off = np.zeros(1, dtype=np.uint32)
-            return off if count_only else (off, np.zeros(0, dtype=KNN_HIT))
-        inp = None
-        if tris is not None or vertices is not None or indices is not None:
-            inp = BuildInput(tri_format, 30, _ptr(tris) if tris is not None else None, _ptr(vertices) if vertices is not None else None,
-                             _ptr(indices) if indices is not None else None, n_vertices, 0)
-        p_inp = C.byref(inp) if inp is not None else None
-        flags = RADIUS_SORTED if sorted else 0
-        what = f"{ALGO_NAMES[self.ALGO]}::radius_search"
-        offsets = ctx.alloc((n + 1) * 4)
-        hits = None
-        try:
-            total = C.c_uint64()
-            if count_only or capacity is None:
-                _check(lib().bvh_radius_search(ctx.handle, C.byref(self.result), p_inp, _ptr(points), n, flags, offsets.ptr, None, 0, C.byref(total)), what)
-                if count_only:
-                    return offsets.download(np.uint32, n + 1)
-                cap = total.value
-            else:
-                cap = int(capacity)
-            for _ in range(2):
-                hits = ctx.alloc(max(cap, 1) * KNN_HIT.itemsize)
-                _check(lib().bvh_radius_search(ctx.handle, C.byref(self.result), p_inp, _ptr(points), n, flags, offsets.ptr, hits.ptr, cap, C.byref(total)), what)
-                if total.value <= cap:
-                    break
-                hits.free(); hits = None
-                cap = total.value
-            return offsets.download(np.uint32, n + 1), hits.download(KNN_HIT, total.value)
-        finally:
-            offsets.free()
-            if hits is not None:
-                hits.free()
-            if own is not None:
-                own.free()
-
+            return _no_queries(count_only, KNN_HIT)
+        inp = _tri_input(tris, vertices, indices, n_vertices, tri_format)
+        res, flags = C.byref(self.result), RADIUS_SORTED if sorted else 0
+        return _count_fill(ctx, lambda off, out, cap, tot: lib().bvh_radius_search(ctx.handle, res, _ref(inp), _ptr(points), n, flags, off, out, cap, tot), n,
+                           KNN_HIT, count_only, capacity, f"{ALGO_NAMES[self.ALGO]}::radius_search", own)
     def _publish(self) -> "_Builder":
         self._free_winding()                              # (a build, refit or optimise: the kept winding moments are stale)
         r, t = self.result, self.timings
@@ -1601,14 +1499,9 @@ class Scene:
     def intersect(self, rays, query="closest", n_rays: int | None = None) -> np.ndarray:
         """bvh_scene_intersect: host RAY array or device buffer (+ n_rays) -> host INSTANCE_HIT array"""
         q = _QUERY_IDS[query] if isinstance(query, str) else int(query)
-        own = None
-        if isinstance(rays, np.ndarray):
-            if rays.dtype != RAY:
-                raise BvhError("rays must have dtype RAY (32-byte records)")
-            n_rays = rays.shape[0]
-            own = rays = self.ctx.upload(np.ascontiguousarray(rays)) if n_rays else None
-        elif n_rays is None:
-            raise BvhError("n_rays is required for device rays")
+        if n_rays is None and not isinstance(rays, np.ndarray):
+            raise BvhError("n_rays is required for device rays")      # (not taken from a DeviceBuffer's size here)
+        rays, n_rays, own = _as_rays(self.ctx, rays, n_rays)
         hits = self.ctx.alloc(max(n_rays, 1) * INSTANCE_HIT.itemsize)
         self._sync_blas()
         try:
@@ -1618,28 +1511,11 @@ class Scene:
             hits.free()
             if own is not None:
                 own.free()
-
     def closest_point(self, points, radius=None, query="closest", n_points: int | None = None) -> np.ndarray:
         """bvh_scene_closest_point: ``points`` as for the builders' closest_point (a host POINT_QUERY array, a host (n, 3) float array whose radius is ``radius``
         (None: +inf), or a device buffer of POINT_QUERY records with ``n_points``) -> host INSTANCE_POINT_HIT array, point and dist2 in world space"""
         q = _QUERY_IDS[query] if isinstance(query, str) else int(query)
-        own = None
-        if isinstance(points, np.ndarray):
-            if points.dtype != POINT_QUERY:
-                xyz = np.asarray(points, dtype=np.float32)
-                if xyz.ndim != 2 or xyz.shape[1] != 3:
-                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
-                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
-                points["point"] = xyz
-                points["radius"] = np.float32(np.inf) if radius is None else np.float32(radius)
-            elif radius is not None:
-                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
-            n_points = points.shape[0]
-            own = points = self.ctx.upload(np.ascontiguousarray(points)) if n_points else None
-        elif n_points is None:
-            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
-            if n_points is None:
-                raise BvhError("n_points is required for device points")
+        points, n_points, own = _as_points(self.ctx, points, radius, n_points)
         hits = self.ctx.alloc(max(n_points, 1) * INSTANCE_POINT_HIT.itemsize)
         self._sync_blas()
         try:
@@ -1649,7 +1525,6 @@ class Scene:
             hits.free()
             if own is not None:
                 own.free()
-
     def knn(self, points, k: int, radius=None, n_points: int | None = None):
         """bvh_scene_knn: the ``k`` (1 .. KNN_MAX_K) nearest triangles within each query's radius over all active instances.  ``points`` as for closest_point
         (a host POINT_QUERY array, a host (n, 3) float array whose radius is ``radius`` (None: +inf), or a device buffer of POINT_QUERY records with
@@ -1658,23 +1533,7 @@ class Scene:
         k = int(k)
         if not 1 <= k <= KNN_MAX_K:
             raise BvhError(f"k must be 1 .. {KNN_MAX_K}")
-        own = None
-        if isinstance(points, np.ndarray):
-            if points.dtype != POINT_QUERY:
-                xyz = np.asarray(points, dtype=np.float32)
-                if xyz.ndim != 2 or xyz.shape[1] != 3:
-                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
-                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
-                points["point"] = xyz
-                points["radius"] = np.float32(np.inf) if radius is None else np.float32(radius)
-            elif radius is not None:
-                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
-            n_points = points.shape[0]
-            own = points = self.ctx.upload(np.ascontiguousarray(points)) if n_points else None
-        elif n_points is None:
-            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
-            if n_points is None:
-                raise BvhError("n_points is required for device points")
+        points, n_points, own = _as_points(self.ctx, points, radius, n_points)
         hits = self.ctx.alloc(max(n_points * k, 1) * INSTANCE_KNN_HIT.itemsize)
         counts = self.ctx.alloc(max(n_points, 1) * 4)
         self._sync_blas()
@@ -1685,56 +1544,19 @@ class Scene:
             hits.free(); counts.free()
             if own is not None:
                 own.free()
-
     def intersect_all(self, rays, sorted: bool = True, count_only: bool = False, capacity: int | None = None, n_rays: int | None = None):
         """bvh_scene_intersect_all: every accepted hit along each ray over all active instances.  ``rays`` a host RAY array or a device buffer (DeviceBuffer /
         int address, with ``n_rays``).  Returns host arrays (offsets u32[n + 1], hits INSTANCE_HIT[total]): ray i's hits are hits[offsets[i]:offsets[i + 1]],
         in ascending (t, instance, prim) order when ``sorted`` (BVH_HITS_SORTED), in no particular order otherwise; an empty slice is a miss.  ``count_only``
         returns offsets alone.  ``capacity`` None: a count-only call first, then a call with the exact capacity; a given capacity that is too small is
         re-allocated with the total the call reported and the call repeated once."""
-        ctx = self.ctx
-        own = None
-        if isinstance(rays, np.ndarray):
-            if rays.dtype != RAY:
-                raise BvhError("rays must have dtype RAY (32-byte records)")
-            n_rays = rays.shape[0]
-            own = rays = ctx.upload(np.ascontiguousarray(rays)) if n_rays else None
-        elif n_rays is None:
-            n_rays = rays.nbytes // RAY.itemsize if isinstance(rays, DeviceBuffer) else None
-            if n_rays is None:
-                raise BvhError("n_rays is required for device rays")
-        if n_rays == 0:                                   # no rays: the empty answer, without a call
-            off = np.zeros(1, dtype=np.uint32)
-            return off if count_only else (off, np.zeros(0, dtype=INSTANCE_HIT))
+        rays, n, own = _as_rays(self.ctx, rays, n_rays)
+        if n == 0:                                        # no rays: the empty answer, without a call
+            return _no_queries(count_only, INSTANCE_HIT)
         flags = HITS_SORTED if sorted else 0
-        what = "bvh_scene_intersect_all"
-        offsets = ctx.alloc((n_rays + 1) * 4)
-        hits = None
         self._sync_blas()
-        try:
-            total = C.c_uint64()
-            if count_only or capacity is None:
-                _check(lib().bvh_scene_intersect_all(self.handle, _ptr(rays), n_rays, flags, offsets.ptr, None, 0, C.byref(total)), what)
-                if count_only:
-                    return offsets.download(np.uint32, n_rays + 1)
-                cap = total.value
-            else:
-                cap = int(capacity)
-            for _ in range(2):
-                hits = ctx.alloc(max(cap, 1) * INSTANCE_HIT.itemsize)
-                _check(lib().bvh_scene_intersect_all(self.handle, _ptr(rays), n_rays, flags, offsets.ptr, hits.ptr, cap, C.byref(total)), what)
-                if total.value <= cap:
-                    break
-                hits.free(); hits = None
-                cap = total.value
-            return offsets.download(np.uint32, n_rays + 1), hits.download(INSTANCE_HIT, total.value)
-        finally:
-            offsets.free()
-            if hits is not None:
-                hits.free()
-            if own is not None:
-                own.free()
-
+        return _count_fill(self.ctx, lambda off, out, cap, tot: lib().bvh_scene_intersect_all(self.handle, _ptr(rays), n, flags, off, out, cap, tot), n,
+                           INSTANCE_HIT, count_only, capacity, "bvh_scene_intersect_all", own)
     def radius_search(self, points, radius=None, sorted: bool = True, count_only: bool = False, capacity: int | None = None, n_points: int | None = None):
         """bvh_scene_radius_search: every triangle of every active instance within each query's radius.  ``points`` as for knn (a host POINT_QUERY array, a
         host (n, 3) float array whose radius is ``radius`` (None: +inf), or a device buffer of POINT_QUERY records with ``n_points``).  Returns host arrays
@@ -1742,56 +1564,13 @@ class Scene:
         when ``sorted`` (BVH_RADIUS_SORTED; quadratic in a slice's length), in no particular order otherwise; an empty slice is "nothing within the radius".
         ``count_only`` returns offsets alone.  ``capacity`` None: a count-only call first, then a call with the exact capacity; a given capacity that is too
         small is re-allocated with the total the call reported and the call repeated once."""
-        ctx = self.ctx
-        own = None
-        if isinstance(points, np.ndarray):
-            if points.dtype != POINT_QUERY:
-                xyz = np.asarray(points, dtype=np.float32)
-                if xyz.ndim != 2 or xyz.shape[1] != 3:
-                    raise BvhError("points must have dtype POINT_QUERY or shape (n, 3)")
-                points = np.zeros(xyz.shape[0], dtype=POINT_QUERY)
-                points["point"] = xyz
-                points["radius"] = np.float32(np.inf) if radius is None else np.float32(radius)
-            elif radius is not None:
-                raise BvhError("radius fills (n, 3) points only: POINT_QUERY records carry their own")
-            n_points = points.shape[0]
-            own = points = ctx.upload(np.ascontiguousarray(points)) if n_points else None
-        elif n_points is None:
-            n_points = points.nbytes // POINT_QUERY.itemsize if isinstance(points, DeviceBuffer) else None
-            if n_points is None:
-                raise BvhError("n_points is required for device points")
-        if n_points == 0:                                 # no points: the empty answer, without a call
-            off = np.zeros(1, dtype=np.uint32)
-            return off if count_only else (off, np.zeros(0, dtype=INSTANCE_KNN_HIT))
+        points, n, own = _as_points(self.ctx, points, radius, n_points)
+        if n == 0:                                        # no points: the empty answer, without a call
+            return _no_queries(count_only, INSTANCE_KNN_HIT)
         flags = RADIUS_SORTED if sorted else 0
-        what = "bvh_scene_radius_search"
-        offsets = ctx.alloc((n_points + 1) * 4)
-        hits = None
         self._sync_blas()
-        try:
-            total = C.c_uint64()
-            if count_only or capacity is None:
-                _check(lib().bvh_scene_radius_search(self.handle, _ptr(points), n_points, flags, offsets.ptr, None, 0, C.byref(total)), what)
-                if count_only:
-                    return offsets.download(np.uint32, n_points + 1)
-                cap = total.value
-            else:
-                cap = int(capacity)
-            for _ in range(2):
-                hits = ctx.alloc(max(cap, 1) * INSTANCE_KNN_HIT.itemsize)
-                _check(lib().bvh_scene_radius_search(self.handle, _ptr(points), n_points, flags, offsets.ptr, hits.ptr, cap, C.byref(total)), what)
-                if total.value <= cap:
-                    break
-                hits.free(); hits = None
-                cap = total.value
-            return offsets.download(np.uint32, n_points + 1), hits.download(INSTANCE_KNN_HIT, total.value)
-        finally:
-            offsets.free()
-            if hits is not None:
-                hits.free()
-            if own is not None:
-                own.free()
-
+        return _count_fill(self.ctx, lambda off, out, cap, tot: lib().bvh_scene_radius_search(self.handle, _ptr(points), n, flags, off, out, cap, tot), n,
+                           INSTANCE_KNN_HIT, count_only, capacity, "bvh_scene_radius_search", own)
     def overlap(self, boxes, sorted: bool = True, count_only: bool = False, capacity: int | None = None, n_boxes: int | None = None):
         """bvh_scene_overlap: every (instance, triangle) pair whose mapped leaf box touches each world-space query box.  ``boxes`` is a host array of n
         boxes ((n, 6) or (n, 2, 3) floats, or dtype AABB) or a device buffer of bvh_aabb records with ``n_boxes``.  Returns host arrays (offsets u32[n + 1],
@@ -1799,52 +1578,13 @@ class Scene:
         (BVH_SCENE_OVERLAP_SORTED; quadratic in a slice's length), in no particular order otherwise; an empty slice is "touches nothing".  ``count_only``
         returns offsets alone.  ``capacity`` None: a count-only call first, then a call with the exact capacity; a given capacity that is too small is
         re-allocated with the total the call reported and the call repeated once."""
-        ctx = self.ctx
-        own = None
-        if isinstance(boxes, np.ndarray):
-            if boxes.dtype != AABB:
-                boxes = np.ascontiguousarray(boxes, dtype=np.float32)
-                if boxes.size % 6 or (boxes.ndim >= 2 and int(np.prod(boxes.shape[1:])) != 6):
-                    raise BvhError("boxes must have dtype AABB or 6 floats per box")
-                boxes = boxes.reshape(-1, 6)
-            n_boxes = boxes.shape[0]
-            own = boxes = ctx.upload(np.ascontiguousarray(boxes)) if n_boxes else None
-        elif n_boxes is None:
-            n_boxes = boxes.nbytes // 24 if isinstance(boxes, DeviceBuffer) else None
-            if n_boxes is None:
-                raise BvhError("n_boxes is required for device boxes")
-        if n_boxes == 0:                                  # no boxes: the empty answer, without a call
-            off = np.zeros(1, dtype=np.uint32)
-            return off if count_only else (off, np.zeros(0, dtype=INSTANCE_PRIM))
+        boxes, n, own = _as_boxes(self.ctx, boxes, n_boxes, "n_boxes", rows_only=False)
+        if n == 0:                                        # no boxes: the empty answer, without a call
+            return _no_queries(count_only, INSTANCE_PRIM)
         flags = SCENE_OVERLAP_SORTED if sorted else 0
-        what = "bvh_scene_overlap"
-        offsets = ctx.alloc((n_boxes + 1) * 4)
-        prims = None
         self._sync_blas()
-        try:
-            total = C.c_uint64()
-            if count_only or capacity is None:
-                _check(lib().bvh_scene_overlap(self.handle, _ptr(boxes), n_boxes, flags, offsets.ptr, None, 0, C.byref(total)), what)
-                if count_only:
-                    return offsets.download(np.uint32, n_boxes + 1)
-                cap = total.value
-            else:
-                cap = int(capacity)
-            for _ in range(2):
-                prims = ctx.alloc(max(cap, 1) * INSTANCE_PRIM.itemsize)
-                _check(lib().bvh_scene_overlap(self.handle, _ptr(boxes), n_boxes, flags, offsets.ptr, prims.ptr, cap, C.byref(total)), what)
-                if total.value <= cap:
-                    break
-                prims.free(); prims = None
-                cap = total.value
-            return offsets.download(np.uint32, n_boxes + 1), prims.download(INSTANCE_PRIM, total.value)
-        finally:
-            offsets.free()
-            if prims is not None:
-                prims.free()
-            if own is not None:
-                own.free()
-
+        return _count_fill(self.ctx, lambda off, out, cap, tot: lib().bvh_scene_overlap(self.handle, _ptr(boxes), n, flags, off, out, cap, tot), n,
+                           INSTANCE_PRIM, count_only, capacity, "bvh_scene_overlap", own)
     def tlas(self) -> Result:
         r = Result()
         _check(lib().bvh_scene_tlas(self.handle, C.byref(r)), "bvh_scene_tlas")

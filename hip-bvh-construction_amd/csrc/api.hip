@@ -214,11 +214,16 @@ void carve(bvh_ctx* c, char* base, uint32_t cap, size_t* total) {
     c->ploc.ids1 = k.take<u32>(n);
     c->ploc.status = k.take<u64>((size_t)PLOC_MAX_ITERS * ploc_chunks(cap));
     c->ploc.state = k.take<u32>(PLOC_STATE_WORDS);
-    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58] bvh_intersect's / bvh_closest_point's / bvh_knn's / bvh_winding_number's overflow count (bvh_overlap / bvh_intersect_all / bvh_radius_search / bvh_scene_intersect_all / bvh_scene_radius_search / bvh_scene_overlap: [58] count pass, [59] fill pass, [60..61] u64 total)
+    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58..61] the query calls' words (overflow_words / total_word below)
     c->hploc.zero_parent = c->small + 1;
     c->overlap_sums = k.take<u64>(OVERLAP_SCAN_BLOCKS);
     *total = k.off;
 }
+// The query calls' words.  Every tree query and every count -> scan -> fill scene query of a ctx shares them (query_tail, count_fill_tail below; bvh_split_refs
+// shares the pinned pairs): calls on one stream are ordered, so a call's kernels and its read-back are done with the words before the next call's memset runs.
+inline u32* overflow_words(const bvh_ctx* c) { return c->small + 58; }                            // queries left to the stackless pass: [0] single pass / count pass, [1] fill pass
+inline u64* total_word(const bvh_ctx* c) { return reinterpret_cast<u64*>(c->small + 60); }        // the count pass's u64 total (small[60..61])
+inline u32* total_pairs(const bvh_ctx* c) { return c->h_pinned + 8; }                             // {lo, ~lo, hi, ~hi} of a total read back: pinned words 8..11
 
 int ensure_capacity(bvh_ctx* c, uint32_t n) {
     if (n <= c->cap) return 0;
@@ -265,11 +270,27 @@ struct Bind { int prev = -1; bool ok = true;
     explicit Bind(int dev) { ok = hipGetDevice(&prev) == hipSuccess && (prev == dev || hipSetDevice(dev) == hipSuccess); }
     ~Bind() { int cur; if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) hipSetDevice(prev); } };
 
+// One tick of the ctx's sampling counter (bvh_ctx_set_kernel_sampling: events in every n-th build or query only) and, while the guard lives, the ctx's kernel
+// recorder installed if this call is a sampled one.  Constructed where a call starts to enqueue: after every argument check and every early return, so that a
+// refused or empty call consumes no tick.  mark() closes the interval of the call's last kernel
+struct Install { bvh_ctx* c; bool sampled, on;
+    explicit Install(bvh_ctx* ctx) : c(ctx), sampled((ctx->build_counter++ % ctx->sample_every) == 0u), on(ctx->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; }
+    void mark() const { if (on) c->recorder.mark(c->stream, nullptr); }
+    void end() { if (on) g_recorder = nullptr; on = false; }
+    ~Install() { end(); } };
+
 static int read_back(bvh_ctx* c, const u32* d_a, u32 na, const u32* d_b, u32 nb, u32* pairs) {
     arm_readback(pairs, na + nb);
     launch_readback(c->stream, d_a, na, d_b, nb, c->d_pinned + (pairs - c->h_pinned));
     HIP_TRY(hipGetLastError());
     return wait_readback(c->stream, pairs, na + nb);
+}
+// the only wait of a count -> scan -> fill call, and only when the caller asks for the total: the u64 at d_total comes back through total_pairs
+static int read_total(bvh_ctx* c, const u64* d_total, uint64_t* total_out) {
+    u32* const rb = total_pairs(c);
+    const int r = read_back(c, reinterpret_cast<const u32*>(d_total), 2, nullptr, 0, rb); if (r) return r;
+    *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
+    return *total_out > 0xFFFFFFFFull ? BVH_E_TOO_LARGE : 0;
 }
 
 // PLOC++ iteration driver: batches of device-side iterations, one small read-back per batch (src/PLOC++Bvh.cpp:132-152
@@ -333,6 +354,110 @@ int stage_extents_fmt(hipStream_t s, const bvh_build_input* in, uint32_t n, void
         case BVH_TRI_INDEXED:  launch_extents_indexed(s, in->d_vertices, in->d_indices, in->n_vertices, n, d_boxes, d_scene, reset_scene, prep); return 0;
         default: return BVH_E_INVALID_ARG;
     }
+}
+
+// what every call that walks a caller-supplied tree requires of it
+inline bool tree_valid(const bvh_result* tree) {
+    const uint32_t n = tree->n_leaves;
+    return !(n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1);
+}
+// the triangles a tree query reads: the caller's (validated) or the tree's own d_tris as Triangle[n]
+int resolve_tris(const bvh_result* tree, const bvh_build_input* tris, bvh_build_input* in) {
+    std::memset(in, 0, sizeof *in);
+    if (tris) { if (stage_extents_valid(tris)) return BVH_E_INVALID_ARG; *in = *tris; }
+    else { if (!tree->d_tris) return BVH_E_INVALID_ARG; in->tri_format = BVH_TRI_PADDED64; in->d_tris = tree->d_tris; }
+    return 0;
+}
+
+// A byte range of memory, for the "these arrays may not overlap" checks.  A null pointer or zero bytes give an empty range, and an empty range crosses nothing.
+struct Range { uintptr_t lo = 0, hi = 0;
+    Range() = default;
+    Range(const void* p, uint64_t bytes) : lo((uintptr_t)p), hi((uintptr_t)p + (p ? bytes : 0u)) {} };
+// does a cross any of the k ranges rs?
+inline bool crosses(const Range& a, const Range* rs, int k) {
+    for (int i = 0; i < k; ++i) if (a.lo < a.hi && rs[i].lo < rs[i].hi && a.lo < rs[i].hi && rs[i].lo < a.hi) return true;
+    return false;
+}
+inline bool crosses(const Range& a, const Range& b) { return crosses(a, &b, 1); }
+// does none of the first m of the k ranges rs (a call's outputs) cross a range after it (m == k: are the k ranges pairwise disjoint?)
+inline bool disjoint(const Range* rs, int m, int k) {
+    for (int a = 0; a < m; ++a) if (crosses(rs[a], rs + a + 1, k - a - 1)) return false;
+    return true;
+}
+// a mesh's one or two arrays of `count` triangles appended to rs; returns how many
+inline int mesh_ranges(const bvh_build_input& m, uint32_t count, Range* rs) {
+    if (m.tri_format != BVH_TRI_INDEXED) { rs[0] = Range(m.d_tris, (uint64_t)count * (m.tri_format == BVH_TRI_PACKED36 ? 36u : 64u)); return 1; }
+    rs[0] = Range(m.d_vertices, (uint64_t)m.n_vertices * 12u); rs[1] = Range(m.d_indices, (uint64_t)count * 12u);
+    return 2;
+}
+// a tree's node array, and its leaf array in layout 1, appended to rs; returns how many
+inline int tree_ranges(const bvh_result* tree, Range* rs) {
+    const uint32_t n = tree->n_leaves;
+    rs[0] = Range(tree->d_nodes, (uint64_t)(tree->layout == 0u ? 2ull * n - 1 : n - 1ull) * sizeof(bvh2_node));
+    if (tree->layout == 1u) rs[1] = Range(tree->d_leaves, (uint64_t)n * sizeof(bvh_primref));
+    return tree->layout == 1u ? 2 : 1;
+}
+// the cap on what a fill pass may write: d_out is never written past 2^32 - 1 records (a larger total skips the fill)
+inline Range fill_range(const void* d_out, uint64_t capacity, size_t record) { return Range(d_out, (capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull) * record); }
+
+// the stackless pass's parent plan: bvh_refit's, cached for the ctx's own tree under the same rule
+void query_plan(bvh_ctx* c, const bvh_result* tree, hipStream_t s) {
+    const bool own = tree->d_nodes == c->nodes;
+    if (!own || c->plan_serial != c->tree_serial || c->plan_n != tree->n_leaves || c->plan_root != tree->root) {
+        launch_refit_plan(s, tree->d_nodes, tree->n_leaves, tree->root, c->parent);
+        c->plan_serial = own ? c->tree_serial : 0; c->plan_n = tree->n_leaves; c->plan_root = tree->root;
+    }
+}
+
+// What a single-pass query does once its arguments are checked and it has queries to answer: bind, tick (Install), the parent plan of a tree query (tree: null for
+// a scene query, whose plans the scene keeps), the overflow word zeroed, launch(stream, overflow).  An error that enqueuing gave is returned; a tree query then
+// also drops the cached plan, which a refused launch may not have written
+template <typename Launch>
+int query_tail(bvh_ctx* c, const bvh_result* tree, u32* overflow, Launch launch) {
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    Install install(c);
+    if (tree) query_plan(c, tree, s);
+    hipError_t e = hipMemsetAsync(overflow, 0, sizeof(u32), s);
+    if (e == hipSuccess) { launch(s, overflow); e = hipGetLastError(); }
+    if (e != hipSuccess) { if (tree) c->plan_serial = 0; return herr(e); }
+    install.mark();
+    return 0;
+}
+
+// What a count -> scan -> fill query does once its arguments are checked.  No queries: d_offsets[0] = total = 0 and nothing else, not even a tick.  Otherwise: tick,
+// the parent plan of a tree query (tree: null for a scene query, which instead makes sure the arena holding the words exists), the four words zeroed,
+// launch(stream, overflow, total) — the count pass and, where the caller gave an output array, the fill pass on overflow + 1 —, errors as query_tail, and the
+// call's only wait: the total's read-back, when the caller asks for it
+template <typename Launch>
+int count_fill_tail(bvh_ctx* c, const bvh_result* tree, uint32_t n_queries, uint32_t* d_offsets, uint64_t* total_out, Launch launch) {
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    if (n_queries == 0) {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
+        if (total_out) *total_out = 0;
+        return 0;
+    }
+    Install install(c);
+    if (tree) query_plan(c, tree, s);
+    // (a one-instance scene on a fresh ctx never made the arena — no top-level build: the smallest one, nothing points into it)
+    else if (!c->arena) { const int r = ensure_capacity(c, 2); if (r) return r; }
+    u32* const overflow = overflow_words(c);
+    u64* const total = total_word(c);
+    hipError_t e = hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s);
+    if (e == hipSuccess) { launch(s, overflow, total); e = hipGetLastError(); }
+    if (e != hipSuccess) { if (tree) c->plan_serial = 0; return herr(e); }
+    install.mark();
+    return total_out ? read_total(c, total, total_out) : 0;
+}
+
+// what every scene query's kernels are handed: the scene's arrays, the n queries and their answers, the overflow word of the pass
+SceneQuery scene_query(const bvh_scene* sc, const void* queries, uint32_t n, void* answers, uint32_t* overflow) {
+    SceneQuery q;
+    q.rays = queries; q.hits = answers; q.overflow = overflow;
+    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
+    q.n_rays = n; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
+    return q;
 }
 
 // per-primitive algorithmic bytes of the whole pipeline (restated in DESIGN.md)
@@ -590,9 +715,8 @@ int bvh_emit_hploc(bvh_ctx* c, const void* d_prim_aabbs, const uint32_t* d_sorte
 static int build_impl(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_t n, bvh_result* out, bvh_timings* tm, const void* d_in_boxes = nullptr) {
     const int key_bits = in->morton_bits == 60 ? 64 : 32;
     hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;      // bvh_ctx_set_kernel_sampling: events in every n-th build only
-    const bool prof = c->profiling && sampled;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    Install install(c);
+    const bool prof = c->profiling && install.sampled;
     uint32_t ploc_iters = 0;
     int r = 0;
     ++c->tree_serial;                                         // (bvh_refit's cached parent plan no longer describes c->nodes)
@@ -650,7 +774,7 @@ static int build_impl(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint
     }
     r = end_emit(c); if (r) return r;
     c->scene_ready = true; c->scene_slot ^= 1;             // every launch was accepted: the Morton kernel has reset the other extent for the next build
-    if (install.on) c->recorder.mark(s, nullptr);
+    install.mark();
     if (prof) HIP_TRY(hipEventRecord(c->ev[4], s));
     if (algo == BVH_LBVH_SINGLEPASS) {   // m_rootNodeIdx read-back (src/SinglePassLbvh.cpp:131)
         r = read_back(c, c->small, 1, nullptr, 0, c->h_pinned); if (r) return r;           // {root, ~root} into pinned words 0..1
@@ -717,10 +841,8 @@ int bvh_build_boxes(bvh_ctx* c, bvh_algo algo, const void* d_boxes, uint32_t n, 
 // what bvh_refit may touch is checked before anything is enqueued: an error changes nothing.  The arena is never re-allocated (io may point into it).
 static int refit_check(const bvh_ctx* c, const bvh_result* io) {
     if (!c || !io) return BVH_E_INVALID_ARG;
-    const uint32_t n = io->n_leaves;
-    if (n < 2 || io->layout > 1u || !io->d_nodes || !io->d_prim_aabbs || !io->d_scene_extent) return BVH_E_INVALID_ARG;
-    if (io->layout == 1u && !io->d_leaves) return BVH_E_INVALID_ARG;
-    if (n > c->cap || io->root >= n - 1) return BVH_E_INVALID_ARG;      // (parent / flags scratch is sized by the capacity: bvh_ctx_reserve first)
+    if (!tree_valid(io) || !io->d_prim_aabbs || !io->d_scene_extent) return BVH_E_INVALID_ARG;
+    if (io->n_leaves > c->cap) return BVH_E_INVALID_ARG;      // (parent / flags scratch is sized by the capacity: bvh_ctx_reserve first)
     return 0;
 }
 // stage E into io's prim boxes and scene extent (the result's own extent slot: the other slot and the ctx's scene bookkeeping are untouched), the parent plan
@@ -728,9 +850,8 @@ static int refit_check(const bvh_ctx* c, const bvh_result* io) {
 static int refit_impl(bvh_ctx* c, bvh_result* io, const bvh_build_input* in, bvh_timings* tm) {
     hipStream_t s = c->stream;
     const uint32_t n = io->n_leaves;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    const bool prof = c->profiling && sampled;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    Install install(c);
+    const bool prof = c->profiling && install.sampled;
     if (prof) HIP_TRY(hipEventRecord(c->ev[0], s));
     int r = stage_extents_fmt(s, in, n, io->d_prim_aabbs, io->d_scene_extent, true, nullptr); if (r) return r;
     if (prof) HIP_TRY(hipEventRecord(c->ev[1], s));
@@ -742,7 +863,7 @@ static int refit_impl(bvh_ctx* c, bvh_result* io, const bvh_build_input* in, bvh
     }
     launch_refit_climb(s, io->d_prim_aabbs, io->d_nodes, io->d_leaves, (int)io->layout, n, c->parent, c->flags);
     r = end_emit(c); if (r) { c->plan_serial = 0; return r; }
-    if (install.on) c->recorder.mark(s, nullptr);
+    install.mark();
     if (prof) HIP_TRY(hipEventRecord(c->ev[4], s));
     io->d_tris = in->tri_format == BVH_TRI_INDEXED ? in->d_vertices : in->d_tris;
     if (tm) {
@@ -807,21 +928,18 @@ int bvh_refit_subset(bvh_ctx* c, bvh_result* io, const bvh_build_input* in, cons
     if ((n_dirty && !d_prims) || n_dirty >= (1u << 30)) return BVH_E_INVALID_ARG;
     const uint32_t n = io->n_leaves;
     {   // the list may not overlap what the call writes
-        const uintptr_t p0 = (uintptr_t)d_prims, p1 = p0 + (uint64_t)n_dirty * sizeof(u32);
-        auto overlaps = [&](const void* a, uint64_t bytes) { const uintptr_t a0 = (uintptr_t)a; return a && n_dirty && p0 < a0 + bytes && a0 < p1; };
-        if (overlaps(io->d_prim_aabbs, (uint64_t)n * sizeof(bvh_aabb)) || overlaps(io->d_scene_extent, sizeof(bvh_aabb)) ||
-            overlaps(io->d_nodes, (uint64_t)(io->layout == 0 ? 2 * (uint64_t)n - 1 : n - 1) * sizeof(bvh2_node)) ||
-            (io->layout == 1 && overlaps(io->d_leaves, (uint64_t)n * sizeof(bvh_primref))) || overlaps(c->parent, (uint64_t)c->cap * 2 * sizeof(u32)) ||
-            overlaps(c->subset_words, (uint64_t)c->subset_cap * 3 * sizeof(u32))) return BVH_E_INVALID_ARG;
+        Range w[6] = { Range(io->d_prim_aabbs, (uint64_t)n * sizeof(bvh_aabb)), Range(io->d_scene_extent, sizeof(bvh_aabb)),
+                       Range(c->parent, (uint64_t)c->cap * 2 * sizeof(u32)), Range(c->subset_words, (uint64_t)c->subset_cap * 3 * sizeof(u32)) };
+        const int k = 4 + tree_ranges(io, w + 4);
+        if (crosses(Range(d_prims, (uint64_t)n_dirty * sizeof(u32)), w, k)) return BVH_E_INVALID_ARG;
     }
     if (n_dirty == 0) return 0;
     Bind b(c->device);
     r = ensure_subset_words(c); if (r) return r;
     hipStream_t s = c->stream;
     u32* const leaf_of_prim = c->subset_words; u32* const owner = leaf_of_prim + c->subset_cap; u32* const pending = owner + c->subset_cap;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    const bool prof = c->profiling && sampled;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    Install install(c);
+    const bool prof = c->profiling && install.sampled;
     const bool own = io->d_nodes == c->nodes;
     // caller-owned arrays may be anything: arrays that are not a tree can leave marks behind, so the call after one of theirs starts from zeroed words
     if (c->subset_dirty) HIP_TRY(hipMemsetAsync(owner, 0, (size_t)c->subset_cap * 2 * sizeof(u32), s));
@@ -843,7 +961,7 @@ int bvh_refit_subset(bvh_ctx* c, bvh_result* io, const bvh_build_input* in, cons
                               io->d_scene_extent);
     { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { c->plan_serial = 0; c->map_serial = 0; return -(int)e; } }
     c->subset_dirty = !own;                                   // (marks that caller-owned arrays left behind never reach the next call, whoever's tree it is on)
-    if (install.on) c->recorder.mark(s, nullptr);
+    install.mark();
     if (prof) HIP_TRY(hipEventRecord(c->ev[4], s));
     io->d_tris = inp.tri_format == BVH_TRI_INDEXED ? inp.d_vertices : inp.d_tris;
     if (tm) {
@@ -868,150 +986,85 @@ int bvh_refit_subset(bvh_ctx* c, bvh_result* io, const bvh_build_input* in, cons
 static int query_check(const bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, int query, const void* d_q, uint64_t q_bytes, const void* d_h,
                        uint64_t h_bytes, bvh_build_input* in) {
     if (!c || !tree || !d_q || !d_h) return BVH_E_INVALID_ARG;
-    const uint32_t n = tree->n_leaves;
-    if (n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1) return BVH_E_INVALID_ARG;
-    std::memset(in, 0, sizeof *in);
-    if (tris) { if (stage_extents_valid(tris)) return BVH_E_INVALID_ARG; *in = *tris; }
-    else { if (!tree->d_tris) return BVH_E_INVALID_ARG; in->tri_format = BVH_TRI_PADDED64; in->d_tris = tree->d_tris; }
+    if (!tree_valid(tree) || resolve_tris(tree, tris, in)) return BVH_E_INVALID_ARG;
     if (query != BVH_QUERY_CLOSEST && query != BVH_QUERY_ANY) return BVH_E_INVALID_ARG;
-    const uintptr_t q0 = (uintptr_t)d_q, q1 = q0 + q_bytes, h0 = (uintptr_t)d_h, h1 = h0 + h_bytes;
-    if (q_bytes && q0 < h1 && h0 < q1) return BVH_E_INVALID_ARG;
-    if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
+    if (crosses(Range(d_q, q_bytes), Range(d_h, h_bytes))) return BVH_E_INVALID_ARG;
+    if (tree->n_leaves > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
     return 0;
-}
-
-// the stackless pass's parent plan: bvh_refit's, cached for the ctx's own tree under the same rule
-static void query_plan(bvh_ctx* c, const bvh_result* tree, hipStream_t s) {
-    const bool own = tree->d_nodes == c->nodes;
-    if (!own || c->plan_serial != c->tree_serial || c->plan_n != tree->n_leaves || c->plan_root != tree->root) {
-        launch_refit_plan(s, tree->d_nodes, tree->n_leaves, tree->root, c->parent);
-        c->plan_serial = own ? c->tree_serial : 0; c->plan_n = tree->n_leaves; c->plan_root = tree->root;
-    }
 }
 
 int bvh_intersect(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_ray* d_rays, uint32_t n_rays, bvh_hit* d_hits, int query) {
     bvh_build_input in;
     int r = query_check(c, tree, tris, query, d_rays, (uint64_t)n_rays * sizeof(bvh_ray), d_hits, (uint64_t)n_rays * sizeof(bvh_hit), &in); if (r) return r;
     if (n_rays == 0) return 0;
-    const uint32_t n = tree->n_leaves;
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    query_plan(c, tree, s);
-    u32* overflow = c->small + 58;                            // rays left to the stackless pass
-    hipError_t e = hipMemsetAsync(overflow, 0, sizeof(u32), s);
-    if (e == hipSuccess) {
-        launch_intersect(s, (int)tree->layout, query, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_rays, n_rays, tree->d_nodes, tree->d_leaves, n, tree->root, d_hits, overflow, c->parent);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
-    if (install.on) c->recorder.mark(s, nullptr);
-    return 0;
+    return query_tail(c, tree, overflow_words(c), [&](hipStream_t s, u32* overflow) {
+        launch_intersect(s, (int)tree->layout, query, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_rays, n_rays, tree->d_nodes, tree->d_leaves,
+                         tree->n_leaves, tree->root, d_hits, overflow, c->parent);
+    });
 }
 
 // ---- point queries (no counterpart in the reference) ----------------------------------------------------------------------------------------------
-// bvh_intersect's checks, plan and launch sequence
+// bvh_intersect's checks and tail
 int bvh_closest_point(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_point_query* d_points, uint32_t n_points, bvh_point_hit* d_hits,
                       int query) {
     bvh_build_input in;
     int r = query_check(c, tree, tris, query, d_points, (uint64_t)n_points * sizeof(bvh_point_query), d_hits, (uint64_t)n_points * sizeof(bvh_point_hit), &in);
     if (r) return r;
     if (n_points == 0) return 0;
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    query_plan(c, tree, s);
-    u32* overflow = c->small + 58;                            // queries left to the stackless pass (bvh_intersect's word: calls on one stream are ordered)
-    hipError_t e = hipMemsetAsync(overflow, 0, sizeof(u32), s);
-    if (e == hipSuccess) {
+    return query_tail(c, tree, overflow_words(c), [&](hipStream_t s, u32* overflow) {
         launch_closest_point(s, (int)tree->layout, query, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_points, n_points,
                              tree->d_nodes, tree->d_leaves, tree->n_leaves, tree->root, d_hits, overflow, c->parent);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
-    if (install.on) c->recorder.mark(s, nullptr);
-    return 0;
+    });
 }
 
 // ---- winding numbers (no counterpart in the reference) ----------------------------------------------------------------------------------------------
 // the tree / triangle checks of query_check and the moments array's own; every argument is checked before anything is enqueued, so an error writes nothing.
-// rg / n_rg: the byte ranges of the tree's and the triangles' arrays, which neither d_moments nor an answer array may overlap
-struct WindRange { uintptr_t lo, hi; };
-static bool wind_overlaps(const WindRange* rg, int n_rg, const void* p, uint64_t bytes) {
-    const uintptr_t lo = (uintptr_t)p, hi = lo + bytes;
-    for (int k = 0; k < n_rg; ++k) if (bytes && rg[k].lo < rg[k].hi && lo < rg[k].hi && rg[k].lo < hi) return true;
-    return false;
-}
-static int winding_check(const bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const void* d_moments, bvh_build_input* in, WindRange* rg, int* n_rg) {
+// rg / n_rg: the byte ranges of the tree's and the triangles' arrays and, last, of d_moments, which may overlap none of them
+static int winding_check(const bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const void* d_moments, bvh_build_input* in, Range* rg, int* n_rg) {
     if (!c || !tree || !d_moments || ((uintptr_t)d_moments & 15u)) return BVH_E_INVALID_ARG;
-    const uint32_t n = tree->n_leaves;
-    if (n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1) return BVH_E_INVALID_ARG;
-    std::memset(in, 0, sizeof *in);
-    if (tris) { if (stage_extents_valid(tris)) return BVH_E_INVALID_ARG; *in = *tris; }
-    else { if (!tree->d_tris) return BVH_E_INVALID_ARG; in->tri_format = BVH_TRI_PADDED64; in->d_tris = tree->d_tris; }
-    if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan and the exchange words live in the arena: bvh_ctx_reserve first)
-    int k = 0;
-    auto add = [&](const void* p, uint64_t bytes) { rg[k].lo = (uintptr_t)p; rg[k].hi = rg[k].lo + bytes; ++k; };
-    add(tree->d_nodes, (uint64_t)(tree->layout == 0u ? 2ull * n - 1 : n - 1ull) * sizeof(bvh2_node));
-    if (tree->layout == 1u) add(tree->d_leaves, (uint64_t)n * sizeof(bvh_primref));
-    if (in->tri_format == BVH_TRI_INDEXED) { add(in->d_vertices, (uint64_t)in->n_vertices * 12u); add(in->d_indices, (uint64_t)n * 12u); }
-    else add(in->d_tris, (uint64_t)n * (in->tri_format == BVH_TRI_PACKED36 ? 36u : 64u));
-    *n_rg = k;
-    if (wind_overlaps(rg, k, d_moments, (uint64_t)(n - 1) * sizeof(bvh_winding_moment))) return BVH_E_INVALID_ARG;
-    return 0;
+    if (!tree_valid(tree) || resolve_tris(tree, tris, in)) return BVH_E_INVALID_ARG;
+    if (tree->n_leaves > c->cap) return BVH_E_INVALID_ARG;    // (the parent plan and the exchange words live in the arena: bvh_ctx_reserve first)
+    int k = tree_ranges(tree, rg);
+    k += mesh_ranges(*in, tree->n_leaves, rg + k);
+    rg[k] = Range(d_moments, (uint64_t)(tree->n_leaves - 1) * sizeof(bvh_winding_moment));
+    *n_rg = k + 1;
+    return crosses(rg[k], rg, k) ? BVH_E_INVALID_ARG : 0;
 }
 
 // bvh_refit's plan (cached under its rule), then the climb on the self-cleaning flags words (begin_emit / end_emit as for a refit) and the finalise
 int bvh_winding_prepare(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, bvh_winding_moment* d_moments) {
-    bvh_build_input in; WindRange rg[4]; int n_rg = 0;
+    bvh_build_input in; Range rg[5]; int n_rg = 0;
     int r = winding_check(c, tree, tris, d_moments, &in, rg, &n_rg); if (r) return r;
     Bind b(c->device);
     hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    Install install(c);
     r = begin_emit(c); if (r) return r;
     query_plan(c, tree, s);
     launch_winding_prepare(s, (int)tree->layout, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, tree->d_nodes, tree->d_leaves,
                            tree->n_leaves, c->parent, c->flags, d_moments);
     r = end_emit(c); if (r) { c->plan_serial = 0; return r; }
-    if (install.on) c->recorder.mark(s, nullptr);
+    install.mark();
     return 0;
 }
 
-// bvh_closest_point's plan and launch sequence (its overflow word: calls on one stream are ordered)
+// bvh_closest_point's tail
 int bvh_winding_number(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_winding_moment* d_moments, const bvh_point_query* d_points,
                        uint32_t n_points, float beta, float* d_w) {
-    bvh_build_input in; WindRange rg[6]; int n_rg = 0;
+    bvh_build_input in; Range rg[6]; int n_rg = 0;
     int r = winding_check(c, tree, tris, d_moments, &in, rg, &n_rg); if (r) return r;
     if (!d_points || !d_w || !(beta >= 0.0f)) return BVH_E_INVALID_ARG;     // (a NaN beta fails the comparison)
-    const uint64_t p_bytes = (uint64_t)n_points * sizeof(bvh_point_query), w_bytes = (uint64_t)n_points * sizeof(float);
-    rg[n_rg].lo = (uintptr_t)d_moments; rg[n_rg].hi = rg[n_rg].lo + (uint64_t)(tree->n_leaves - 1) * sizeof(bvh_winding_moment); ++n_rg;
-    if (wind_overlaps(rg + n_rg - 1, 1, d_points, p_bytes)) return BVH_E_INVALID_ARG;
-    rg[n_rg].lo = (uintptr_t)d_points; rg[n_rg].hi = rg[n_rg].lo + p_bytes; ++n_rg;
-    if (wind_overlaps(rg, n_rg, d_w, w_bytes)) return BVH_E_INVALID_ARG;
+    rg[n_rg] = Range(d_points, (uint64_t)n_points * sizeof(bvh_point_query));
+    if (crosses(rg[n_rg], rg[n_rg - 1])) return BVH_E_INVALID_ARG;          // the points against the moments; the answers against everything
+    if (crosses(Range(d_w, (uint64_t)n_points * sizeof(float)), rg, n_rg + 1)) return BVH_E_INVALID_ARG;
     if (n_points == 0) return 0;
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    query_plan(c, tree, s);
-    u32* overflow = c->small + 58;                            // queries left to the stackless pass
-    hipError_t e = hipMemsetAsync(overflow, 0, sizeof(u32), s);
-    if (e == hipSuccess) {
+    return query_tail(c, tree, overflow_words(c), [&](hipStream_t s, u32* overflow) {
         launch_winding(s, (int)tree->layout, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_points, n_points, tree->d_nodes,
                        tree->d_leaves, tree->n_leaves, tree->root, d_moments, beta, d_w, overflow, c->parent);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
-    if (install.on) c->recorder.mark(s, nullptr);
-    return 0;
+    });
 }
 
 // ---- k-nearest queries (no counterpart in the reference) -------------------------------------------------------------------------------------------
-// bvh_closest_point's checks (query_check with the lists as the answer array) plus k's range, the list array's size and the third range; then its plan and
-// launch sequence
+// bvh_closest_point's checks (query_check with the lists as the answer array) plus k's range, the list array's size and the third range; then its tail
 int bvh_knn(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_point_query* d_points, uint32_t n_points, uint32_t k, bvh_knn_hit* d_hits,
             uint32_t* d_counts) {
     if (k == 0u || k > (uint32_t)BVH_KNN_MAX_K) return BVH_E_INVALID_ARG;
@@ -1020,259 +1073,118 @@ int bvh_knn(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, con
     bvh_build_input in;
     int r = query_check(c, tree, tris, BVH_QUERY_CLOSEST, d_points, p_bytes, d_hits, h_bytes, &in);
     if (r) return r;
-    if (d_counts && n_points) {                               // the third range: against the points and against the lists
-        const uintptr_t c0 = (uintptr_t)d_counts, c1 = c0 + (uint64_t)n_points * sizeof(u32);
-        const uintptr_t p0 = (uintptr_t)d_points, p1 = p0 + p_bytes, h0 = (uintptr_t)d_hits, h1 = h0 + h_bytes;
-        if ((c0 < p1 && p0 < c1) || (c0 < h1 && h0 < c1)) return BVH_E_INVALID_ARG;
-    }
+    const Range ph[2] = { Range(d_points, p_bytes), Range(d_hits, h_bytes) };
+    if (crosses(Range(d_counts, (uint64_t)n_points * sizeof(u32)), ph, 2)) return BVH_E_INVALID_ARG;     // the third range: against the points and against the lists
     if (n_points == 0) return 0;
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    query_plan(c, tree, s);
-    u32* overflow = c->small + 58;                            // queries left to the stackless pass (bvh_intersect's word: calls on one stream are ordered)
-    hipError_t e = hipMemsetAsync(overflow, 0, sizeof(u32), s);
-    if (e == hipSuccess) {
+    return query_tail(c, tree, overflow_words(c), [&](hipStream_t s, u32* overflow) {
         launch_knn(s, (int)tree->layout, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_points, n_points, k, tree->d_nodes,
                    tree->d_leaves, tree->n_leaves, tree->root, d_hits, d_counts, overflow, c->parent);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
-    if (install.on) c->recorder.mark(s, nullptr);
-    return 0;
+    });
 }
 
 // ---- box queries (no counterpart in the reference) ------------------------------------------------------------------------------------------------
-// count -> scan -> fill on one stream; every argument is checked before anything is enqueued, so an error writes nothing.  The arena is never re-allocated (the
-// tree may point into it).  Whether the fill runs is decided on the device (overlap.hip); the host only waits when the caller asks for the total.
+// count -> scan -> fill on one stream (count_fill_tail); every argument is checked before anything is enqueued, so an error writes nothing.  The arena is never
+// re-allocated (the tree may point into it).  Whether the fill runs is decided on the device (overlap.hip); the host only waits when the caller asks for the total.
 int bvh_overlap(bvh_ctx* c, const bvh_result* tree, const bvh_aabb* d_boxes, uint32_t n_boxes, int mode, uint32_t* d_offsets, uint32_t* d_prims,
                 uint64_t capacity, uint64_t* total_out) {
     if (!c || !tree || !d_boxes || !d_offsets) return BVH_E_INVALID_ARG;
+    if (!tree_valid(tree)) return BVH_E_INVALID_ARG;
     const uint32_t n = tree->n_leaves;
-    if (n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1) return BVH_E_INVALID_ARG;
     if (mode != BVH_OVERLAP_BOXES && mode != BVH_OVERLAP_SELF) return BVH_E_INVALID_ARG;
     if (mode == BVH_OVERLAP_SELF && n_boxes != n) return BVH_E_INVALID_ARG;
     if (n_boxes >= (1u << 30)) return BVH_E_INVALID_ARG;
     if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
-    {   // the three caller arrays must not overlap (d_prims is never written past 2^32 - 1 words: a larger total skips the fill)
-        struct Range { uintptr_t lo, hi; };
-        const uint64_t prim_words = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;
-        const Range rb{ (uintptr_t)d_boxes, (uintptr_t)d_boxes + (uint64_t)n_boxes * sizeof(bvh_aabb) };
-        const Range ro{ (uintptr_t)d_offsets, (uintptr_t)d_offsets + ((uint64_t)n_boxes + 1u) * sizeof(u32) };
-        const Range rp{ (uintptr_t)d_prims, (uintptr_t)d_prims + (d_prims ? prim_words * sizeof(u32) : 0u) };
-        auto cross = [](const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; };
-        if (cross(rb, ro) || cross(rb, rp) || cross(ro, rp)) return BVH_E_INVALID_ARG;
-    }
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    if (n_boxes == 0) {                                       // d_offsets[0] = total = 0, nothing else
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
-        if (total_out) *total_out = 0;
-        return 0;
-    }
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    query_plan(c, tree, s);
-    u32* const overflow = c->small + 58;                      // [0] count pass, [1] fill pass: queries left to the stackless pass
-    u64* const total = reinterpret_cast<u64*>(c->small + 60);
-    hipError_t e = hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s);
-    if (e == hipSuccess) {
+    const Range rs[3] = { Range(d_boxes, (uint64_t)n_boxes * sizeof(bvh_aabb)), Range(d_offsets, ((uint64_t)n_boxes + 1u) * sizeof(u32)),
+                          fill_range(d_prims, capacity, sizeof(u32)) };
+    if (!disjoint(rs, 3, 3)) return BVH_E_INVALID_ARG;        // the three caller arrays must not overlap
+    return count_fill_tail(c, tree, n_boxes, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
         launch_overlap_count(s, (int)tree->layout, mode, d_boxes, n_boxes, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, overflow, c->parent,
                              c->overlap_sums, total);
         if (d_prims)
             launch_overlap_fill(s, (int)tree->layout, mode, d_boxes, n_boxes, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, d_prims, capacity, total,
                                 overflow + 1, c->parent);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
-    if (install.on) c->recorder.mark(s, nullptr);
-    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
-        u32* const rb = c->h_pinned + 8;
-        const int r = read_back(c, c->small + 60, 2, nullptr, 0, rb); if (r) return r;
-        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
-        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
-    }
-    return 0;
+    });
 }
 
 // ---- crossing triangle pairs (no counterpart in the reference) -------------------------------------------------------------------------------------
-// bvh_overlap's count -> scan -> fill sequence, overflow words, total word and read-back, with the query mesh's triangles in place of boxes; every argument is
-// checked before anything is enqueued, so an error writes nothing.  Neither output array may overlap the other or any array the call reads
+// bvh_overlap's tail, with the query mesh's triangles in place of boxes; every argument is checked before anything is enqueued, so an error writes nothing.
+// Neither output array may overlap the other or any array the call reads
 int bvh_intersect_tris(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_build_input* queries, uint32_t n_queries, int mode,
                        uint32_t* d_offsets, uint32_t* d_prims, uint64_t capacity, uint64_t* total_out) {
     if (!c || !tree || !d_offsets) return BVH_E_INVALID_ARG;
     if (mode != BVH_TRIS_QUERY && mode != BVH_TRIS_SELF) return BVH_E_INVALID_ARG;
     if ((mode == BVH_TRIS_SELF) != (queries == nullptr)) return BVH_E_INVALID_ARG;       // the other mesh, or none in self mode
+    if (!tree_valid(tree)) return BVH_E_INVALID_ARG;
     const uint32_t n = tree->n_leaves;
-    if (n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1) return BVH_E_INVALID_ARG;
     if (mode == BVH_TRIS_SELF && n_queries != n) return BVH_E_INVALID_ARG;
     if (n_queries >= (1u << 30)) return BVH_E_INVALID_ARG;
-    bvh_build_input in; std::memset(&in, 0, sizeof in);
-    if (tris) { if (stage_extents_valid(tris)) return BVH_E_INVALID_ARG; in = *tris; }
-    else { if (!tree->d_tris) return BVH_E_INVALID_ARG; in.tri_format = BVH_TRI_PADDED64; in.d_tris = tree->d_tris; }
+    bvh_build_input in;
+    if (resolve_tris(tree, tris, &in)) return BVH_E_INVALID_ARG;
     bvh_build_input qin = in;                                 // (self mode: the tree's own triangles)
     if (queries) { if (stage_extents_valid(queries)) return BVH_E_INVALID_ARG; qin = *queries; }
     if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
-    {   // the output arrays against each other and against everything the call reads (d_prims is never written past 2^32 - 1 words: a larger total skips the fill)
-        WindRange rg[9]; int k = 0;
-        auto add = [&](const void* p, uint64_t bytes) { rg[k].lo = (uintptr_t)p; rg[k].hi = rg[k].lo + bytes; ++k; };
-        auto add_mesh = [&](const bvh_build_input& m, uint32_t count) {
-            if (m.tri_format == BVH_TRI_INDEXED) { add(m.d_vertices, (uint64_t)m.n_vertices * 12u); add(m.d_indices, (uint64_t)count * 12u); }
-            else add(m.d_tris, (uint64_t)count * (m.tri_format == BVH_TRI_PACKED36 ? 36u : 64u));
-        };
-        add(tree->d_nodes, (uint64_t)(tree->layout == 0u ? 2ull * n - 1 : n - 1ull) * sizeof(bvh2_node));
-        if (tree->layout == 1u) add(tree->d_leaves, (uint64_t)n * sizeof(bvh_primref));
-        add_mesh(in, n);
-        if (queries) add_mesh(qin, n_queries);
-        const uint64_t off_bytes = ((uint64_t)n_queries + 1u) * sizeof(u32);
-        const uint64_t prim_bytes = d_prims ? (capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull) * sizeof(u32) : 0u;
-        if (wind_overlaps(rg, k, d_offsets, off_bytes) || wind_overlaps(rg, k, d_prims, prim_bytes)) return BVH_E_INVALID_ARG;
-        add(d_offsets, off_bytes);
-        if (wind_overlaps(rg + k - 1, 1, d_prims, prim_bytes)) return BVH_E_INVALID_ARG;
+    {   // the output arrays against each other and against everything the call reads
+        Range rs[8] = { Range(d_offsets, ((uint64_t)n_queries + 1u) * sizeof(u32)), fill_range(d_prims, capacity, sizeof(u32)) };
+        int k = 2 + tree_ranges(tree, rs + 2);
+        k += mesh_ranges(in, n, rs + k);
+        if (queries) k += mesh_ranges(qin, n_queries, rs + k);
+        if (!disjoint(rs, 2, k)) return BVH_E_INVALID_ARG;
     }
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    if (n_queries == 0) {                                     // d_offsets[0] = total = 0, nothing else
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
-        if (total_out) *total_out = 0;
-        return 0;
-    }
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    query_plan(c, tree, s);
-    u32* const overflow = c->small + 58;                      // bvh_overlap's words: [0] count pass, [1] fill pass (calls on one stream are ordered)
-    u64* const total = reinterpret_cast<u64*>(c->small + 60);
     const TrisMesh tm{ (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices };
     const TrisMesh qm{ (int)qin.tri_format, qin.d_tris, qin.d_vertices, qin.d_indices, qin.n_vertices };
-    hipError_t e = hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s);
-    if (e == hipSuccess) {
+    return count_fill_tail(c, tree, n_queries, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
         launch_tris_count(s, (int)tree->layout, mode, tm, qm, n_queries, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, overflow, c->parent,
                           c->overlap_sums, total);
         if (d_prims)
             launch_tris_fill(s, (int)tree->layout, mode, tm, qm, n_queries, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, d_prims, capacity, total,
                              overflow + 1, c->parent);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
-    if (install.on) c->recorder.mark(s, nullptr);
-    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
-        u32* const rb = c->h_pinned + 8;
-        const int r = read_back(c, c->small + 60, 2, nullptr, 0, rb); if (r) return r;
-        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
-        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
-    }
-    return 0;
+    });
 }
 
 // ---- all-hits ray queries (no counterpart in the reference) ---------------------------------------------------------------------------------------
-// bvh_intersect's tree / triangle checks and bvh_overlap's count -> scan -> fill sequence, overflow words, total word and read-back; every argument is checked
-// before anything is enqueued, so an error writes nothing
+// bvh_intersect's tree / triangle checks and bvh_overlap's tail; every argument is checked before anything is enqueued, so an error writes nothing
 int bvh_intersect_all(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_ray* d_rays, uint32_t n_rays, uint32_t flags,
                       uint32_t* d_offsets, bvh_hit* d_hits, uint64_t capacity, uint64_t* total_out) {
     if (!c || !tree || !d_rays || !d_offsets) return BVH_E_INVALID_ARG;
     if (flags & ~BVH_HITS_SORTED) return BVH_E_INVALID_ARG;
     if (n_rays >= (1u << 30)) return BVH_E_INVALID_ARG;
+    bvh_build_input in;
+    if (!tree_valid(tree) || resolve_tris(tree, tris, &in)) return BVH_E_INVALID_ARG;
     const uint32_t n = tree->n_leaves;
-    if (n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1) return BVH_E_INVALID_ARG;
-    bvh_build_input in; std::memset(&in, 0, sizeof in);
-    if (tris) { if (stage_extents_valid(tris)) return BVH_E_INVALID_ARG; in = *tris; }
-    else { if (!tree->d_tris) return BVH_E_INVALID_ARG; in.tri_format = BVH_TRI_PADDED64; in.d_tris = tree->d_tris; }
     if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
-    {   // the three caller arrays must not overlap (d_hits is never written past 2^32 - 1 records: a larger total skips the fill)
-        struct Range { uintptr_t lo, hi; };
-        const uint64_t recs = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;
-        const Range rr{ (uintptr_t)d_rays, (uintptr_t)d_rays + (uint64_t)n_rays * sizeof(bvh_ray) };
-        const Range ro{ (uintptr_t)d_offsets, (uintptr_t)d_offsets + ((uint64_t)n_rays + 1u) * sizeof(u32) };
-        const Range rh{ (uintptr_t)d_hits, (uintptr_t)d_hits + (d_hits ? recs * sizeof(bvh_hit) : 0u) };
-        auto cross = [](const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; };
-        if (cross(rr, ro) || cross(rr, rh) || cross(ro, rh)) return BVH_E_INVALID_ARG;
-    }
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    if (n_rays == 0) {                                        // d_offsets[0] = total = 0, nothing else
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
-        if (total_out) *total_out = 0;
-        return 0;
-    }
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    query_plan(c, tree, s);
-    u32* const overflow = c->small + 58;                      // bvh_overlap's words: [0] count pass, [1] fill pass (calls on one stream are ordered)
-    u64* const total = reinterpret_cast<u64*>(c->small + 60);
-    hipError_t e = hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s);
-    if (e == hipSuccess) {
+    const Range rs[3] = { Range(d_rays, (uint64_t)n_rays * sizeof(bvh_ray)), Range(d_offsets, ((uint64_t)n_rays + 1u) * sizeof(u32)),
+                          fill_range(d_hits, capacity, sizeof(bvh_hit)) };
+    if (!disjoint(rs, 3, 3)) return BVH_E_INVALID_ARG;        // the three caller arrays must not overlap
+    return count_fill_tail(c, tree, n_rays, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
         launch_hits_count(s, (int)tree->layout, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_rays, n_rays, tree->d_nodes,
                           tree->d_leaves, n, tree->root, d_offsets, overflow, c->parent, c->overlap_sums, total);
         if (d_hits)
             launch_hits_fill(s, (int)tree->layout, (int)in.tri_format, (flags & BVH_HITS_SORTED) ? 1 : 0, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices,
                              d_rays, n_rays, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, d_hits, capacity, total, overflow + 1, c->parent);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
-    if (install.on) c->recorder.mark(s, nullptr);
-    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
-        u32* const rb = c->h_pinned + 8;
-        const int r = read_back(c, c->small + 60, 2, nullptr, 0, rb); if (r) return r;
-        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
-        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
-    }
-    return 0;
+    });
 }
 
 // ---- radius searches (no counterpart in the reference) -------------------------------------------------------------------------------------------
-// bvh_closest_point's tree / triangle checks and bvh_intersect_all's count -> scan -> fill sequence, overflow words, total word and read-back; every argument is
-// checked before anything is enqueued, so an error writes nothing
+// bvh_closest_point's tree / triangle checks and bvh_intersect_all's tail; every argument is checked before anything is enqueued, so an error writes nothing
 int bvh_radius_search(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_point_query* d_points, uint32_t n_points, uint32_t flags,
                       uint32_t* d_offsets, bvh_knn_hit* d_hits, uint64_t capacity, uint64_t* total_out) {
     if (!c || !tree || !d_points || !d_offsets) return BVH_E_INVALID_ARG;
     if (flags & ~BVH_RADIUS_SORTED) return BVH_E_INVALID_ARG;
     if (n_points >= (1u << 30)) return BVH_E_INVALID_ARG;
+    bvh_build_input in;
+    if (!tree_valid(tree) || resolve_tris(tree, tris, &in)) return BVH_E_INVALID_ARG;
     const uint32_t n = tree->n_leaves;
-    if (n < 2 || tree->layout > 1u || !tree->d_nodes || (tree->layout == 1u && !tree->d_leaves) || tree->root >= n - 1) return BVH_E_INVALID_ARG;
-    bvh_build_input in; std::memset(&in, 0, sizeof in);
-    if (tris) { if (stage_extents_valid(tris)) return BVH_E_INVALID_ARG; in = *tris; }
-    else { if (!tree->d_tris) return BVH_E_INVALID_ARG; in.tri_format = BVH_TRI_PADDED64; in.d_tris = tree->d_tris; }
     if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
-    {   // the three caller arrays must not overlap (d_hits is never written past 2^32 - 1 records: a larger total skips the fill)
-        struct Range { uintptr_t lo, hi; };
-        const uint64_t recs = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;
-        const Range rp{ (uintptr_t)d_points, (uintptr_t)d_points + (uint64_t)n_points * sizeof(bvh_point_query) };
-        const Range ro{ (uintptr_t)d_offsets, (uintptr_t)d_offsets + ((uint64_t)n_points + 1u) * sizeof(u32) };
-        const Range rh{ (uintptr_t)d_hits, (uintptr_t)d_hits + (d_hits ? recs * sizeof(bvh_knn_hit) : 0u) };
-        auto cross = [](const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; };
-        if (cross(rp, ro) || cross(rp, rh) || cross(ro, rh)) return BVH_E_INVALID_ARG;
-    }
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    if (n_points == 0) {                                      // d_offsets[0] = total = 0, nothing else
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
-        if (total_out) *total_out = 0;
-        return 0;
-    }
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    query_plan(c, tree, s);
-    u32* const overflow = c->small + 58;                      // bvh_overlap's words: [0] count pass, [1] fill pass (calls on one stream are ordered)
-    u64* const total = reinterpret_cast<u64*>(c->small + 60);
-    hipError_t e = hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s);
-    if (e == hipSuccess) {
+    const Range rs[3] = { Range(d_points, (uint64_t)n_points * sizeof(bvh_point_query)), Range(d_offsets, ((uint64_t)n_points + 1u) * sizeof(u32)),
+                          fill_range(d_hits, capacity, sizeof(bvh_knn_hit)) };
+    if (!disjoint(rs, 3, 3)) return BVH_E_INVALID_ARG;        // the three caller arrays must not overlap
+    return count_fill_tail(c, tree, n_points, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
         launch_radius_count(s, (int)tree->layout, (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices, d_points, n_points, tree->d_nodes,
                             tree->d_leaves, n, tree->root, d_offsets, overflow, c->parent, c->overlap_sums, total);
         if (d_hits)
             launch_radius_fill(s, (int)tree->layout, (int)in.tri_format, (flags & BVH_RADIUS_SORTED) ? 1 : 0, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices,
                                d_points, n_points, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, d_hits, capacity, total, overflow + 1, c->parent);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { c->plan_serial = 0; return herr(e); }
-    if (install.on) c->recorder.mark(s, nullptr);
-    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
-        u32* const rb = c->h_pinned + 8;
-        const int r = read_back(c, c->small + 60, 2, nullptr, 0, rb); if (r) return r;
-        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
-        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
-    }
-    return 0;
+    });
 }
 
 // ---- early split clipping (Utility::doEarlySplitClipping, src/Utility.cpp:456-538, as a device pass) ----------------------------------------------
@@ -1301,28 +1213,14 @@ int bvh_split_refs(bvh_ctx* c, const bvh_build_input* in, uint32_t n, float sa_m
     if (!(sa_max >= 0.0f)) return BVH_E_INVALID_ARG;          // (NaN or negative)
     if (max_depth > (uint32_t)BVH_SPLIT_MAX_DEPTH) return BVH_E_INVALID_ARG;
     if ((d_ref_boxes == nullptr) != (d_ref_prims == nullptr)) return BVH_E_INVALID_ARG;
-    {   // the output ranges may not overlap each other, d_offsets or the input (the outputs are never written past 2^32 - 1 records: a larger total skips the fill)
-        struct Range { uintptr_t lo, hi; };
-        const uint64_t recs = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;
-        const Range ro{ (uintptr_t)d_offsets, (uintptr_t)d_offsets + ((uint64_t)n + 1u) * sizeof(u32) };
-        const Range rb{ (uintptr_t)d_ref_boxes, (uintptr_t)d_ref_boxes + (d_ref_boxes ? recs * sizeof(bvh_aabb) : 0u) };
-        const Range rp{ (uintptr_t)d_ref_prims, (uintptr_t)d_ref_prims + (d_ref_prims ? recs * sizeof(u32) : 0u) };
-        Range i0{ 0, 0 }, i1{ 0, 0 };
-        switch (in->tri_format) {
-            case BVH_TRI_PADDED64: i0 = { (uintptr_t)in->d_tris, (uintptr_t)in->d_tris + (uint64_t)n * 64u }; break;
-            case BVH_TRI_PACKED36: i0 = { (uintptr_t)in->d_tris, (uintptr_t)in->d_tris + (uint64_t)n * 36u }; break;
-            default: i0 = { (uintptr_t)in->d_vertices, (uintptr_t)in->d_vertices + (uint64_t)in->n_vertices * 12u };
-                     i1 = { (uintptr_t)in->d_indices, (uintptr_t)in->d_indices + (uint64_t)n * 12u }; break;
-        }
-        auto cross = [](const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; };
-        if (cross(ro, rb) || cross(ro, rp) || cross(rb, rp) || cross(ro, i0) || cross(ro, i1) || cross(rb, i0) || cross(rb, i1) || cross(rp, i0) || cross(rp, i1))
-            return BVH_E_INVALID_ARG;
+    {   // the output ranges may not overlap each other, d_offsets or the input
+        Range rs[5] = { Range(d_offsets, ((uint64_t)n + 1u) * sizeof(u32)), fill_range(d_ref_boxes, capacity, sizeof(bvh_aabb)), fill_range(d_ref_prims, capacity, sizeof(u32)) };
+        if (!disjoint(rs, 3, 3 + mesh_ranges(*in, n, rs + 3))) return BVH_E_INVALID_ARG;
     }
     Bind b(c->device);
     int r = ensure_split_words(c, n); if (r) return r;
     hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    Install install(c);
     u64* const total = reinterpret_cast<u64*>(c->split_words);
     u32* const heavy_count = reinterpret_cast<u32*>(c->split_words + 8);
     u64* const sums = reinterpret_cast<u64*>(c->split_words + 64);
@@ -1337,14 +1235,8 @@ int bvh_split_refs(bvh_ctx* c, const bvh_build_input* in, uint32_t n, float sa_m
         e = hipGetLastError();
     }
     if (e != hipSuccess) return herr(e);
-    if (install.on) c->recorder.mark(s, nullptr);
-    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
-        u32* const rb = c->h_pinned + 8;
-        r = read_back(c, reinterpret_cast<const u32*>(total), 2, nullptr, 0, rb); if (r) return r;
-        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
-        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
-    }
-    return 0;
+    install.mark();
+    return total_out ? read_total(c, total, total_out) : 0;
 }
 
 // ---- batched small-mesh builds (no working counterpart in the reference: src/BatchedBuildKernel.h:218-312 is what this was meant to be) ------------------------------
@@ -1375,19 +1267,7 @@ int many_check(bvh_algo algo, const bvh_build_input* in, uint32_t n_tris, const 
     return many_check_input(in, n_tris, h_meshes, n_meshes, lay);
 }
 // six output arrays, then the input's one or two: an output may overlap neither another output nor the input
-struct ManyRange { uintptr_t lo, hi; };
-inline ManyRange many_range(const void* p, uint64_t bytes) { return ManyRange{ (uintptr_t)p, (uintptr_t)p + (p ? bytes : 0u) }; }
-inline void many_input_ranges(const bvh_build_input* in, uint32_t n_tris, ManyRange rs[2]) {
-    const bool indexed = in->tri_format == BVH_TRI_INDEXED;
-    rs[0] = indexed ? many_range(in->d_vertices, (uint64_t)in->n_vertices * 12u) : many_range(in->d_tris, (uint64_t)n_tris * (in->tri_format == BVH_TRI_PADDED64 ? 64u : 36u));
-    rs[1] = indexed ? many_range(in->d_indices, (uint64_t)n_tris * 12u) : ManyRange{ 0, 0 };
-}
-inline bool many_overlap(const ManyRange rs[8]) {
-    for (int a = 0; a < 6; ++a)
-        for (int b = a + 1; b < 8; ++b)
-            if (rs[a].lo < rs[a].hi && rs[b].lo < rs[b].hi && rs[a].lo < rs[b].hi && rs[b].lo < rs[a].hi) return true;
-    return false;
-}
+inline bool many_overlap(Range rs[8], const bvh_build_input* in, uint32_t n_tris) { return !disjoint(rs, 6, 6 + mesh_ranges(*in, n_tris, rs + 6)); }
 // the output arrays of either call: LBVH (bvh_many_out: leaves NULL, mesh m's 2n-1 node records from record 2*out_off - m) or PLOC++ (bvh_many_ploc_out: roots NULL,
 // n-1 node records from record out_off - m)
 struct ManyOutAny { void* nodes; void* leaves; void* boxes; void* scenes; uint32_t* roots; uint32_t* skeys; uint32_t* svals; };
@@ -1412,8 +1292,8 @@ static int many_build(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, cons
         c->many_items = d; c->many_host = h; c->many_cap = n_small;
     } else if (n_small) HIP_TRY(hipEventSynchronize(c->many_ev));   // the previous call's copy has read the pinned words
     if (lay.n_large) { r = ensure_capacity(c, lay.max_large); if (r) return r; }
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    const bool prof = c->profiling && sampled;
+    Install install(c);
+    const bool prof = c->profiling && install.sampled;
     if (prof) HIP_TRY(hipEventRecord(c->ev[5], s));
     if (n_small) {
         uint32_t at[4] = { 0u, lay.n_class[0], lay.n_class[0] + lay.n_class[1], lay.n_class[0] + lay.n_class[1] + lay.n_class[2] };
@@ -1425,7 +1305,6 @@ static int many_build(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, cons
         }
         HIP_TRY(hipMemcpyAsync(c->many_items, c->many_host, (size_t)n_small * sizeof(uint4), hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(c->many_ev, s));
-        struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
         if (ploc) {
             ManyPlocArgs a;
             a.tris = in->d_tris; a.verts = in->d_vertices; a.idx = in->d_indices; a.n_verts = in->n_vertices;
@@ -1440,8 +1319,9 @@ static int many_build(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, cons
             launch_many(s, a, (int)in->tri_format, karras, c->many_items, lay.n_class);
         }
         HIP_TRY(hipGetLastError());
-        if (install.on) c->recorder.mark(s, nullptr);
+        install.mark();
     }
+    install.end();                                            // (the large meshes' builds tick and record for themselves)
     if (lay.n_large) {                                        // the ordinary build on the ctx (its arena, its read-backs), one mesh after another, copied to the slice
         uint32_t off = 0;
         for (uint32_t m = 0; m < n_meshes; ++m) {
@@ -1486,12 +1366,11 @@ int bvh_build_many(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, uint32_
     if (!c) return BVH_E_INVALID_ARG;
     ManyLayout lay;
     int r = many_check(algo, in, n_tris, h_meshes, n_meshes, out, &lay); if (r) return r;
-    ManyRange rs[8] = {
-        many_range(out->d_nodes, (2ull * lay.total - n_meshes) * sizeof(bvh2_node)), many_range(out->d_prim_aabbs, lay.total * sizeof(bvh_aabb)),
-        many_range(out->d_scene_extents, (uint64_t)n_meshes * sizeof(bvh_aabb)), many_range(out->d_roots, (uint64_t)n_meshes * sizeof(u32)),
-        many_range(out->d_sorted_keys, lay.total * sizeof(u32)), many_range(out->d_sorted_vals, lay.total * sizeof(u32)) };
-    many_input_ranges(in, n_tris, rs + 6);
-    if (many_overlap(rs)) return BVH_E_INVALID_ARG;
+    Range rs[8] = {
+        Range(out->d_nodes, (2ull * lay.total - n_meshes) * sizeof(bvh2_node)), Range(out->d_prim_aabbs, lay.total * sizeof(bvh_aabb)),
+        Range(out->d_scene_extents, (uint64_t)n_meshes * sizeof(bvh_aabb)), Range(out->d_roots, (uint64_t)n_meshes * sizeof(u32)),
+        Range(out->d_sorted_keys, lay.total * sizeof(u32)), Range(out->d_sorted_vals, lay.total * sizeof(u32)) };
+    if (many_overlap(rs, in, n_tris)) return BVH_E_INVALID_ARG;
     const ManyOutAny o = { out->d_nodes, nullptr, out->d_prim_aabbs, out->d_scene_extents, out->d_roots, out->d_sorted_keys, out->d_sorted_vals };
     return many_build(c, algo, in, h_meshes, n_meshes, o, lay, tm);
 }
@@ -1502,12 +1381,11 @@ int bvh_build_many_ploc(bvh_ctx* c, bvh_algo algo, const bvh_build_input* in, ui
     if (!out->d_nodes || !out->d_leaves || !out->d_prim_aabbs || !out->d_scene_extents) return BVH_E_INVALID_ARG;
     ManyLayout lay;
     int r = many_check_input(in, n_tris, h_meshes, n_meshes, &lay); if (r) return r;
-    ManyRange rs[8] = {
-        many_range(out->d_nodes, (lay.total - n_meshes) * sizeof(bvh2_node)), many_range(out->d_leaves, lay.total * sizeof(bvh_primref)),
-        many_range(out->d_prim_aabbs, lay.total * sizeof(bvh_aabb)), many_range(out->d_scene_extents, (uint64_t)n_meshes * sizeof(bvh_aabb)),
-        many_range(out->d_sorted_keys, lay.total * sizeof(u32)), many_range(out->d_sorted_vals, lay.total * sizeof(u32)) };
-    many_input_ranges(in, n_tris, rs + 6);
-    if (many_overlap(rs)) return BVH_E_INVALID_ARG;
+    Range rs[8] = {
+        Range(out->d_nodes, (lay.total - n_meshes) * sizeof(bvh2_node)), Range(out->d_leaves, lay.total * sizeof(bvh_primref)),
+        Range(out->d_prim_aabbs, lay.total * sizeof(bvh_aabb)), Range(out->d_scene_extents, (uint64_t)n_meshes * sizeof(bvh_aabb)),
+        Range(out->d_sorted_keys, lay.total * sizeof(u32)), Range(out->d_sorted_vals, lay.total * sizeof(u32)) };
+    if (many_overlap(rs, in, n_tris)) return BVH_E_INVALID_ARG;
     const ManyOutAny o = { out->d_nodes, out->d_leaves, out->d_prim_aabbs, out->d_scene_extents, nullptr, out->d_sorted_keys, out->d_sorted_vals };
     return many_build(c, algo, in, h_meshes, n_meshes, o, lay, tm);
 }
@@ -1577,17 +1455,15 @@ int bvh_remap_leaves(bvh_ctx* c, bvh_result* io, const uint32_t* d_map, uint32_t
     const uint32_t n = io->n_leaves;
     {   // the map may not overlap the leaf records
         const char* w = io->layout == 0 ? (const char*)io->d_nodes + (uint64_t)(n - 1) * sizeof(bvh2_node) : (const char*)io->d_leaves;
-        const uint64_t w_bytes = (uint64_t)n * (io->layout == 0 ? sizeof(bvh2_node) : sizeof(bvh_primref)), m_bytes = (uint64_t)n_map * sizeof(u32);
-        const uintptr_t w0 = (uintptr_t)w, m0 = (uintptr_t)d_map;
-        if (n_map && m0 < w0 + w_bytes && w0 < m0 + m_bytes) return BVH_E_INVALID_ARG;
+        const uint64_t w_bytes = (uint64_t)n * (io->layout == 0 ? sizeof(bvh2_node) : sizeof(bvh_primref));
+        if (crosses(Range(d_map, (uint64_t)n_map * sizeof(u32)), Range(w, w_bytes))) return BVH_E_INVALID_ARG;
     }
     Bind b(c->device);
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    Install install(c);
     c->map_serial = 0;
     launch_remap_leaves(c->stream, io->d_nodes, io->d_leaves, (int)io->layout, n, d_map, n_map);
     HIP_TRY(hipGetLastError());
-    if (install.on) c->recorder.mark(c->stream, nullptr);
+    install.mark();
     return 0;
 }
 
@@ -1597,15 +1473,14 @@ int bvh_remap_leaves(bvh_ctx* c, bvh_result* io, const uint32_t* d_map, uint32_t
 // THEIR tree in `parent`, which the ctx's own tree does not use (plan_serial 0, as after a refit of caller-owned arrays).
 int bvh_optimize(bvh_ctx* c, bvh_result* io, uint32_t rounds, bvh_timings* tm) {
     if (!c || !io) return BVH_E_INVALID_ARG;
+    if (!tree_valid(io)) return BVH_E_INVALID_ARG;
     const uint32_t n = io->n_leaves;
-    if (n < 2 || io->layout > 1u || !io->d_nodes || (io->layout == 1u && !io->d_leaves) || io->root >= n - 1) return BVH_E_INVALID_ARG;
     if (rounds < 1u || rounds > 8u) return BVH_E_INVALID_ARG;
     if (n > c->cap) return BVH_E_INVALID_ARG;                 // (parent / flags scratch is sized by the capacity: bvh_ctx_reserve first)
     Bind b(c->device);
     hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    const bool prof = c->profiling && sampled;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
+    Install install(c);
+    const bool prof = c->profiling && install.sampled;
     if (prof) HIP_TRY(hipEventRecord(c->ev[1], s));
     int r = begin_emit(c); if (r) return r;
     const bool own = io->d_nodes == c->nodes;
@@ -1617,7 +1492,7 @@ int bvh_optimize(bvh_ctx* c, bvh_result* io, uint32_t rounds, bvh_timings* tm) {
     for (uint32_t k = 0; k < rounds && (7u << k) <= n; ++k, ++ran)       // (a round whose gamma exceeds n has no treelet root: not launched)
         launch_optimize(s, io->d_nodes, io->d_leaves, (int)io->layout, n, 7u << k, c->parent, c->flags);
     r = end_emit(c); if (r) { c->plan_serial = 0; return r; }
-    if (install.on) c->recorder.mark(s, nullptr);
+    install.mark();
     if (prof) HIP_TRY(hipEventRecord(c->ev[4], s));
     if (tm) {
         std::memset(tm, 0, sizeof *tm);
@@ -1649,29 +1524,19 @@ void bvh_scene_destroy(bvh_scene* sc) {
 }
 
 namespace {
-inline bool ranges_overlap(const void* p, uint64_t bytes, const void* q, uint64_t qbytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return p && q && bytes && qbytes && a < b + qbytes && b < a + bytes;
-}
 // one bvh_blas -> its device descriptor; BVH_E_INVALID_ARG for what bvh_intersect would reject and for arrays inside the ctx's arena / triangle staging buffer
 int blas_descriptor(const bvh_ctx* c, const bvh_blas& in, SceneBlas& d) {
     const bvh_result& t = in.tree;
     const uint32_t n = t.n_leaves;
-    if (n < 2 || n >= (1u << 30) || t.layout > 1u || !t.d_nodes || (t.layout == 1u && !t.d_leaves) || t.root >= n - 1) return BVH_E_INVALID_ARG;
+    if (!tree_valid(&t) || n >= (1u << 30)) return BVH_E_INVALID_ARG;
     bvh_build_input tri = in.tris;
     if (tri.tri_format == BVH_TRI_PADDED64 && !tri.d_tris) tri.d_tris = t.d_tris;
     if (stage_extents_valid(&tri)) return BVH_E_INVALID_ARG;
-    const uint64_t node_bytes = (uint64_t)(t.layout == 0 ? 2ull * n - 1 : n - 1ull) * sizeof(bvh2_node), leaf_bytes = t.layout == 1 ? (uint64_t)n * sizeof(bvh_primref) : 0;
-    const void* arrays[4] = { t.d_nodes, t.layout == 1 ? t.d_leaves : nullptr, nullptr, nullptr };
-    uint64_t sizes[4] = { node_bytes, leaf_bytes, 0, 0 };
-    switch (tri.tri_format) {
-        case BVH_TRI_PADDED64: arrays[2] = tri.d_tris; sizes[2] = (uint64_t)n * 64; break;
-        case BVH_TRI_PACKED36: arrays[2] = tri.d_tris; sizes[2] = (uint64_t)n * 36; break;
-        default: arrays[2] = tri.d_vertices; sizes[2] = (uint64_t)tri.n_vertices * 12; arrays[3] = tri.d_indices; sizes[3] = (uint64_t)n * 12; break;
-    }
-    for (int k = 0; k < 4; ++k)
-        if (ranges_overlap(arrays[k], sizes[k], c->arena, c->arena_bytes) || ranges_overlap(arrays[k], sizes[k], c->tris, (uint64_t)c->tris_cap * sizeof(bvh_triangle)))
-            return BVH_E_INVALID_ARG;
+    const Range own[2] = { Range(c->arena, c->arena_bytes), Range(c->tris, (uint64_t)c->tris_cap * sizeof(bvh_triangle)) };
+    Range arrays[4];
+    int k = tree_ranges(&t, arrays);
+    k += mesh_ranges(tri, n, arrays + k);
+    for (int a = 0; a < k; ++a) if (crosses(arrays[a], own, 2)) return BVH_E_INVALID_ARG;
     std::memset(&d, 0, sizeof d);
     d.nodes = t.d_nodes; d.leaves = t.layout == 1 ? t.d_leaves : nullptr; d.tris = tri.tri_format == BVH_TRI_INDEXED ? tri.d_vertices : tri.d_tris;
     d.idx = tri.tri_format == BVH_TRI_INDEXED ? tri.d_indices : nullptr;
@@ -1764,46 +1629,17 @@ int bvh_scene_update(bvh_scene* sc, const bvh_instance* instances, int on_device
 int bvh_scene_intersect(bvh_scene* sc, const bvh_ray* d_rays, uint32_t n_rays, bvh_instance_hit* d_hits, int query) {
     if (!sc || !d_rays || !d_hits || !sc->built) return BVH_E_INVALID_ARG;
     if (query != BVH_QUERY_CLOSEST && query != BVH_QUERY_ANY) return BVH_E_INVALID_ARG;
-    const uintptr_t r0 = (uintptr_t)d_rays, r1 = r0 + (uint64_t)n_rays * sizeof(bvh_ray), h0 = (uintptr_t)d_hits, h1 = h0 + (uint64_t)n_rays * sizeof(bvh_instance_hit);
-    if (n_rays && r0 < h1 && h0 < r1) return BVH_E_INVALID_ARG;
+    if (crosses(Range(d_rays, (uint64_t)n_rays * sizeof(bvh_ray)), Range(d_hits, (uint64_t)n_rays * sizeof(bvh_instance_hit)))) return BVH_E_INVALID_ARG;
     if (n_rays == 0) return 0;
-    bvh_ctx* c = sc->ctx;
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    HIP_TRY(hipMemsetAsync(sc->overflow, 0, sizeof(u32), s));
-    SceneQuery q;
-    q.rays = d_rays; q.hits = d_hits; q.overflow = sc->overflow;
-    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
-    q.n_rays = n_rays; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
-    launch_scene_intersect(s, query, q);
-    HIP_TRY(hipGetLastError());
-    if (install.on) c->recorder.mark(s, nullptr);
-    return 0;
+    return query_tail(sc->ctx, nullptr, sc->overflow, [&](hipStream_t s, u32* overflow) { launch_scene_intersect(s, query, scene_query(sc, d_rays, n_rays, d_hits, overflow)); });
 }
 
 int bvh_scene_closest_point(bvh_scene* sc, const bvh_point_query* d_points, uint32_t n_points, bvh_instance_point_hit* d_hits, int query) {
     if (!sc || !d_points || !d_hits || !sc->built) return BVH_E_INVALID_ARG;
     if (query != BVH_QUERY_CLOSEST && query != BVH_QUERY_ANY) return BVH_E_INVALID_ARG;
-    const uintptr_t p0 = (uintptr_t)d_points, p1 = p0 + (uint64_t)n_points * sizeof(bvh_point_query), h0 = (uintptr_t)d_hits,
-                    h1 = h0 + (uint64_t)n_points * sizeof(bvh_instance_point_hit);
-    if (n_points && p0 < h1 && h0 < p1) return BVH_E_INVALID_ARG;
+    if (crosses(Range(d_points, (uint64_t)n_points * sizeof(bvh_point_query)), Range(d_hits, (uint64_t)n_points * sizeof(bvh_instance_point_hit)))) return BVH_E_INVALID_ARG;
     if (n_points == 0) return 0;
-    bvh_ctx* c = sc->ctx;
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    HIP_TRY(hipMemsetAsync(sc->overflow, 0, sizeof(u32), s));
-    SceneQuery q;
-    q.rays = d_points; q.hits = d_hits; q.overflow = sc->overflow;
-    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
-    q.n_rays = n_points; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
-    launch_scene_closest_point(s, query, q);
-    HIP_TRY(hipGetLastError());
-    if (install.on) c->recorder.mark(s, nullptr);
-    return 0;
+    return query_tail(sc->ctx, nullptr, sc->overflow, [&](hipStream_t s, u32* overflow) { launch_scene_closest_point(s, query, scene_query(sc, d_points, n_points, d_hits, overflow)); });
 }
 
 // bvh_scene_closest_point's scene and bvh_knn's argument rules; every argument is checked before anything is enqueued, so an error writes nothing
@@ -1811,178 +1647,64 @@ int bvh_scene_knn(bvh_scene* sc, const bvh_point_query* d_points, uint32_t n_poi
     if (!sc || !d_points || !d_hits || !sc->built) return BVH_E_INVALID_ARG;
     if (k == 0u || k > (uint32_t)BVH_KNN_MAX_K) return BVH_E_INVALID_ARG;
     if ((uint64_t)n_points * k >= (1ull << 32)) return BVH_E_INVALID_ARG;
-    if (n_points) {                                           // the three caller arrays must not overlap
-        const uint64_t p_bytes = (uint64_t)n_points * sizeof(bvh_point_query), h_bytes = (uint64_t)n_points * k * sizeof(bvh_instance_knn_hit);
-        const uintptr_t p0 = (uintptr_t)d_points, p1 = p0 + p_bytes, h0 = (uintptr_t)d_hits, h1 = h0 + h_bytes;
-        if (p0 < h1 && h0 < p1) return BVH_E_INVALID_ARG;
-        if (d_counts) {
-            const uintptr_t c0 = (uintptr_t)d_counts, c1 = c0 + (uint64_t)n_points * sizeof(u32);
-            if ((c0 < p1 && p0 < c1) || (c0 < h1 && h0 < c1)) return BVH_E_INVALID_ARG;
-        }
-    }
+    const Range rs[3] = { Range(d_points, (uint64_t)n_points * sizeof(bvh_point_query)), Range(d_hits, (uint64_t)n_points * k * sizeof(bvh_instance_knn_hit)),
+                          Range(d_counts, (uint64_t)n_points * sizeof(u32)) };
+    if (!disjoint(rs, 3, 3)) return BVH_E_INVALID_ARG;        // the three caller arrays must not overlap
     if (n_points == 0) return 0;
-    bvh_ctx* c = sc->ctx;
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    HIP_TRY(hipMemsetAsync(sc->overflow, 0, sizeof(u32), s));
-    SceneQuery q;
-    q.rays = d_points; q.hits = d_hits; q.overflow = sc->overflow;
-    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
-    q.n_rays = n_points; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
-    q.counts = d_counts; q.k = k;
-    launch_scene_knn(s, q);
-    HIP_TRY(hipGetLastError());
-    if (install.on) c->recorder.mark(s, nullptr);
-    return 0;
+    return query_tail(sc->ctx, nullptr, sc->overflow, [&](hipStream_t s, u32* overflow) {
+        SceneQuery q = scene_query(sc, d_points, n_points, d_hits, overflow);
+        q.counts = d_counts; q.k = k;
+        launch_scene_knn(s, q);
+    });
 }
 
-// bvh_scene_intersect's scene and bvh_intersect_all's count -> scan -> fill sequence, overflow words, total word and read-back (the ctx's words: a scene is
-// bound to one ctx and one stream, whose calls are ordered); every argument is checked before anything is enqueued, so an error writes nothing
+// bvh_scene_intersect's scene and bvh_intersect_all's tail (the ctx's words: a scene is bound to one ctx and one stream, whose calls are ordered); every argument
+// is checked before anything is enqueued, so an error writes nothing
 int bvh_scene_intersect_all(bvh_scene* sc, const bvh_ray* d_rays, uint32_t n_rays, uint32_t flags, uint32_t* d_offsets, bvh_instance_hit* d_hits,
                             uint64_t capacity, uint64_t* total_out) {
     if (!sc || !d_rays || !d_offsets || !sc->built) return BVH_E_INVALID_ARG;
     if (flags & ~BVH_HITS_SORTED) return BVH_E_INVALID_ARG;
     if (n_rays >= (1u << 30)) return BVH_E_INVALID_ARG;
-    {   // the three caller arrays must not overlap (d_hits is never written past 2^32 - 1 records: a larger total skips the fill)
-        struct Range { uintptr_t lo, hi; };
-        const uint64_t recs = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;
-        const Range rr{ (uintptr_t)d_rays, (uintptr_t)d_rays + (uint64_t)n_rays * sizeof(bvh_ray) };
-        const Range ro{ (uintptr_t)d_offsets, (uintptr_t)d_offsets + ((uint64_t)n_rays + 1u) * sizeof(u32) };
-        const Range rh{ (uintptr_t)d_hits, (uintptr_t)d_hits + (d_hits ? recs * sizeof(bvh_instance_hit) : 0u) };
-        auto cross = [](const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; };
-        if (cross(rr, ro) || cross(rr, rh) || cross(ro, rh)) return BVH_E_INVALID_ARG;
-    }
-    bvh_ctx* c = sc->ctx;
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    if (n_rays == 0) {                                        // d_offsets[0] = total = 0, nothing else
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
-        if (total_out) *total_out = 0;
-        return 0;
-    }
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    // the scratch words live in the ctx's arena, which a one-instance scene on a fresh ctx never made (no top-level build): the smallest one, nothing points into it
-    if (!c->arena) { const int r = ensure_capacity(c, 2); if (r) return r; }
-    u32* const overflow = c->small + 58;                      // bvh_overlap's words: [0] count pass, [1] fill pass
-    u64* const total = reinterpret_cast<u64*>(c->small + 60);
-    HIP_TRY(hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s));
-    SceneQuery q;
-    q.rays = d_rays; q.hits = d_hits; q.overflow = overflow;
-    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
-    q.n_rays = n_rays; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
-    const SceneHits h{ d_offsets, d_hits, total, capacity };
-    launch_scene_hits_count(s, q, h, c->overlap_sums, total);
-    if (d_hits) { q.overflow = overflow + 1; launch_scene_hits_fill(s, (flags & BVH_HITS_SORTED) ? 1 : 0, q, h); }
-    HIP_TRY(hipGetLastError());
-    if (install.on) c->recorder.mark(s, nullptr);
-    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
-        u32* const rb = c->h_pinned + 8;
-        const int r = read_back(c, c->small + 60, 2, nullptr, 0, rb); if (r) return r;
-        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
-        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
-    }
-    return 0;
+    const Range rs[3] = { Range(d_rays, (uint64_t)n_rays * sizeof(bvh_ray)), Range(d_offsets, ((uint64_t)n_rays + 1u) * sizeof(u32)), fill_range(d_hits, capacity, sizeof(bvh_instance_hit)) };
+    if (!disjoint(rs, 3, 3)) return BVH_E_INVALID_ARG;        // the three caller arrays must not overlap
+    return count_fill_tail(sc->ctx, nullptr, n_rays, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
+        SceneQuery q = scene_query(sc, d_rays, n_rays, d_hits, overflow);
+        const SceneHits h{ d_offsets, d_hits, total, capacity };
+        launch_scene_hits_count(s, q, h, sc->ctx->overlap_sums, total);
+        if (d_hits) { q.overflow = overflow + 1; launch_scene_hits_fill(s, (flags & BVH_HITS_SORTED) ? 1 : 0, q, h); }
+    });
 }
 
-// bvh_scene_closest_point's scene and points, bvh_scene_intersect_all's count -> scan -> fill sequence, overflow words, total word and read-back (the ctx's
-// words); every argument is checked before anything is enqueued, so an error writes nothing
+// bvh_scene_closest_point's scene and points, bvh_scene_intersect_all's tail; every argument is checked before anything is enqueued, so an error writes nothing
 int bvh_scene_radius_search(bvh_scene* sc, const bvh_point_query* d_points, uint32_t n_points, uint32_t flags, uint32_t* d_offsets, bvh_instance_knn_hit* d_hits,
                             uint64_t capacity, uint64_t* total_out) {
     if (!sc || !d_points || !d_offsets || !sc->built) return BVH_E_INVALID_ARG;
     if (flags & ~BVH_RADIUS_SORTED) return BVH_E_INVALID_ARG;
     if (n_points >= (1u << 30)) return BVH_E_INVALID_ARG;
-    {   // the three caller arrays must not overlap (d_hits is never written past 2^32 - 1 records: a larger total skips the fill)
-        struct Range { uintptr_t lo, hi; };
-        const uint64_t recs = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;
-        const Range rp{ (uintptr_t)d_points, (uintptr_t)d_points + (uint64_t)n_points * sizeof(bvh_point_query) };
-        const Range ro{ (uintptr_t)d_offsets, (uintptr_t)d_offsets + ((uint64_t)n_points + 1u) * sizeof(u32) };
-        const Range rh{ (uintptr_t)d_hits, (uintptr_t)d_hits + (d_hits ? recs * sizeof(bvh_instance_knn_hit) : 0u) };
-        auto cross = [](const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; };
-        if (cross(rp, ro) || cross(rp, rh) || cross(ro, rh)) return BVH_E_INVALID_ARG;
-    }
-    bvh_ctx* c = sc->ctx;
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    if (n_points == 0) {                                      // d_offsets[0] = total = 0, nothing else
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
-        if (total_out) *total_out = 0;
-        return 0;
-    }
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    // (bvh_scene_intersect_all: a one-instance scene on a fresh ctx never made the arena the scratch words live in: the smallest one, nothing points into it)
-    if (!c->arena) { const int r = ensure_capacity(c, 2); if (r) return r; }
-    u32* const overflow = c->small + 58;                      // bvh_overlap's words: [0] count pass, [1] fill pass
-    u64* const total = reinterpret_cast<u64*>(c->small + 60);
-    HIP_TRY(hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s));
-    SceneQuery q;
-    q.rays = d_points; q.hits = d_hits; q.overflow = overflow;
-    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
-    q.n_rays = n_points; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
-    const SceneHits h{ d_offsets, d_hits, total, capacity };
-    launch_scene_radius_count(s, q, h, c->overlap_sums, total);
-    if (d_hits) { q.overflow = overflow + 1; launch_scene_radius_fill(s, (flags & BVH_RADIUS_SORTED) ? 1 : 0, q, h); }
-    HIP_TRY(hipGetLastError());
-    if (install.on) c->recorder.mark(s, nullptr);
-    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
-        u32* const rb = c->h_pinned + 8;
-        const int r = read_back(c, c->small + 60, 2, nullptr, 0, rb); if (r) return r;
-        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
-        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
-    }
-    return 0;
+    const Range rs[3] = { Range(d_points, (uint64_t)n_points * sizeof(bvh_point_query)), Range(d_offsets, ((uint64_t)n_points + 1u) * sizeof(u32)), fill_range(d_hits, capacity, sizeof(bvh_instance_knn_hit)) };
+    if (!disjoint(rs, 3, 3)) return BVH_E_INVALID_ARG;        // the three caller arrays must not overlap
+    return count_fill_tail(sc->ctx, nullptr, n_points, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
+        SceneQuery q = scene_query(sc, d_points, n_points, d_hits, overflow);
+        const SceneHits h{ d_offsets, d_hits, total, capacity };
+        launch_scene_radius_count(s, q, h, sc->ctx->overlap_sums, total);
+        if (d_hits) { q.overflow = overflow + 1; launch_scene_radius_fill(s, (flags & BVH_RADIUS_SORTED) ? 1 : 0, q, h); }
+    });
 }
 
-// bvh_overlap's query boxes on a scene, bvh_scene_radius_search's count -> scan -> fill sequence, overflow words, total word and read-back (the ctx's words);
-// every argument is checked before anything is enqueued, so an error writes nothing
+// bvh_overlap's query boxes on a scene, bvh_scene_radius_search's tail; every argument is checked before anything is enqueued, so an error writes nothing
 int bvh_scene_overlap(bvh_scene* sc, const bvh_aabb* d_boxes, uint32_t n_boxes, uint32_t flags, uint32_t* d_offsets, bvh_instance_prim* d_prims,
                       uint64_t capacity, uint64_t* total_out) {
     if (!sc || !d_boxes || !d_offsets || !sc->built) return BVH_E_INVALID_ARG;
     if (flags & ~BVH_SCENE_OVERLAP_SORTED) return BVH_E_INVALID_ARG;
     if (n_boxes >= (1u << 30)) return BVH_E_INVALID_ARG;
-    {   // the three caller arrays must not overlap (d_prims is never written past 2^32 - 1 records: a larger total skips the fill)
-        struct Range { uintptr_t lo, hi; };
-        const uint64_t recs = capacity < 0xFFFFFFFFull ? capacity : 0xFFFFFFFFull;
-        const Range rq{ (uintptr_t)d_boxes, (uintptr_t)d_boxes + (uint64_t)n_boxes * sizeof(bvh_aabb) };
-        const Range ro{ (uintptr_t)d_offsets, (uintptr_t)d_offsets + ((uint64_t)n_boxes + 1u) * sizeof(u32) };
-        const Range rh{ (uintptr_t)d_prims, (uintptr_t)d_prims + (d_prims ? recs * sizeof(bvh_instance_prim) : 0u) };
-        auto cross = [](const Range& a, const Range& b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; };
-        if (cross(rq, ro) || cross(rq, rh) || cross(ro, rh)) return BVH_E_INVALID_ARG;
-    }
-    bvh_ctx* c = sc->ctx;
-    Bind b(c->device);
-    hipStream_t s = c->stream;
-    if (n_boxes == 0) {                                       // d_offsets[0] = total = 0, nothing else
-        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), s));
-        if (total_out) *total_out = 0;
-        return 0;
-    }
-    const bool sampled = (c->build_counter++ % c->sample_every) == 0u;
-    struct Install { bool on; explicit Install(bvh_ctx* c, bool sampled) : on(c->kernel_profiling && sampled) { if (on) g_recorder = &c->recorder; } ~Install() { if (on) g_recorder = nullptr; } } install(c, sampled);
-    // (bvh_scene_radius_search: a one-instance scene on a fresh ctx never made the arena the scratch words live in: the smallest one, nothing points into it)
-    if (!c->arena) { const int r = ensure_capacity(c, 2); if (r) return r; }
-    u32* const overflow = c->small + 58;                      // bvh_overlap's words: [0] count pass, [1] fill pass
-    u64* const total = reinterpret_cast<u64*>(c->small + 60);
-    HIP_TRY(hipMemsetAsync(overflow, 0, 4 * sizeof(u32), s));
-    SceneQuery q;
-    q.rays = d_boxes; q.hits = d_prims; q.overflow = overflow;
-    q.tnodes = sc->tnodes; q.tleaves = sc->tleaves; q.tparent = sc->tparent; q.inst = sc->inst; q.blas = sc->blas; q.wbox = sc->wbox;
-    q.n_rays = n_boxes; q.n_inst = sc->n_inst; q.troot = sc->troot; q.tlayout = sc->tlayout; q.inst_in = sc->inst_in;
-    const SceneHits h{ d_offsets, d_prims, total, capacity };
-    launch_scene_overlap_count(s, q, h, c->overlap_sums, total);
-    if (d_prims) { q.overflow = overflow + 1; launch_scene_overlap_fill(s, (flags & BVH_SCENE_OVERLAP_SORTED) ? 1 : 0, q, h); }
-    HIP_TRY(hipGetLastError());
-    if (install.on) c->recorder.mark(s, nullptr);
-    if (total_out) {                                          // the only wait of the call: {lo, hi} of the total as pairs at pinned words 8..11
-        u32* const rb = c->h_pinned + 8;
-        const int r = read_back(c, c->small + 60, 2, nullptr, 0, rb); if (r) return r;
-        *total_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
-        if (*total_out > 0xFFFFFFFFull) return BVH_E_TOO_LARGE;
-    }
-    return 0;
+    const Range rs[3] = { Range(d_boxes, (uint64_t)n_boxes * sizeof(bvh_aabb)), Range(d_offsets, ((uint64_t)n_boxes + 1u) * sizeof(u32)), fill_range(d_prims, capacity, sizeof(bvh_instance_prim)) };
+    if (!disjoint(rs, 3, 3)) return BVH_E_INVALID_ARG;        // the three caller arrays must not overlap
+    return count_fill_tail(sc->ctx, nullptr, n_boxes, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
+        SceneQuery q = scene_query(sc, d_boxes, n_boxes, d_prims, overflow);
+        const SceneHits h{ d_offsets, d_prims, total, capacity };
+        launch_scene_overlap_count(s, q, h, sc->ctx->overlap_sums, total);
+        if (d_prims) { q.overflow = overflow + 1; launch_scene_overlap_fill(s, (flags & BVH_SCENE_OVERLAP_SORTED) ? 1 : 0, q, h); }
+    });
 }
 
 int bvh_scene_tlas(const bvh_scene* sc, bvh_result* out) {
