@@ -80,7 +80,7 @@ EXPORTS = [
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
-    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap",
+    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap", "bvh_scene_intersect_tris",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
@@ -125,6 +125,8 @@ TRIS_QUERY, TRIS_SELF = 0, 1         # bvh_tris_mode (bvh_intersect_tris)
 HITS_SORTED = 1                      # BVH_HITS_SORTED (bvh_intersect_all's flag)
 RADIUS_SORTED = 1                    # BVH_RADIUS_SORTED (bvh_radius_search's and bvh_scene_radius_search's flag)
 SCENE_OVERLAP_SORTED = 1             # BVH_SCENE_OVERLAP_SORTED (bvh_scene_overlap's flag)
+SCENE_TRIS_QUERY, SCENE_TRIS_INSTANCE = 0, 1   # bvh_scene_tris_mode (bvh_scene_intersect_tris)
+SCENE_TRIS_SORTED = 1                # BVH_SCENE_TRIS_SORTED (bvh_scene_intersect_tris's flag)
 SPLIT_MAX_DEPTH = 16                 # BVH_SPLIT_MAX_DEPTH (bvh_split_refs)
 ABI_VERSION = 4                      # BVH_ABI_VERSION of include/bvh_mi355x.h this binding was written against
 # bvh_option (bvh_ctx_set_option) and the names this harness accepts for the values
@@ -239,6 +241,7 @@ def lib() -> C.CDLL:
         "bvh_scene_intersect_all": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_scene_radius_search": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_scene_overlap": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_scene_intersect_tris": ([vp, C.POINTER(BuildInput), u32, i32, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
@@ -389,6 +392,30 @@ def _as_boxes(ctx, boxes, n, name="n", rows_only=True):
             boxes = f.reshape(-1, 6)
         return _uploaded(ctx, boxes)
     return boxes, _device_count(boxes, n, AABB.itemsize, name, "boxes"), None
+
+
+def _as_mesh(ctx, other, tri_format, vertices, indices, n, without):
+    """the query mesh of an intersect_tris call: a host TRIANGLE array, host floats ((m, 9) or (m, 3, 3), uploaded as TRI_PACKED36), device records in
+    ``tri_format`` or a device TRI_INDEXED mesh (``vertices`` / ``indices``), the device ones with their count ``n`` unless a DeviceBuffer's size gives it ->
+    (device pointer or buffer, tri_format, n, the buffer uploaded for the call or None).  ``without``: the argument that goes without a mesh, for the message"""
+    own = None
+    if isinstance(other, np.ndarray):
+        if other.dtype == TRIANGLE:
+            tri_format = TRI_PADDED64
+        else:
+            f = np.asarray(other, dtype=np.float32)
+            if f.ndim not in (2, 3) or f.size != f.shape[0] * 9:
+                raise BvhError("other must have dtype TRIANGLE or shape (m, 9) / (m, 3, 3)")
+            other, tri_format = f.reshape(-1, 9), TRI_PACKED36
+        other, n, own = _uploaded(ctx, other)
+    elif other is None and vertices is None and indices is None:
+        raise BvhError(f"another mesh is required (only {without} goes without)")
+    elif n is None:
+        stride = {TRI_PADDED64: 64, TRI_PACKED36: 36}.get(tri_format)
+        n = other.nbytes // stride if isinstance(other, DeviceBuffer) and stride else (indices.nbytes // 12 if isinstance(indices, DeviceBuffer) else None)
+        if n is None:
+            raise BvhError("n is required for a device mesh")
+    return other, tri_format, n, own
 
 
 def _count_fill(ctx, call, n, rec_dtype, count_only, capacity, what, own=None):
@@ -1193,22 +1220,7 @@ class _Builder:
                 raise BvhError("self_pairs=True is not available on a build_split tree: it has more leaves than triangles; pass the mesh as `other` instead")
             n = self.result.n_leaves
         else:
-            if isinstance(other, np.ndarray):
-                if other.dtype == TRIANGLE:
-                    tri_format = TRI_PADDED64
-                else:
-                    f = np.asarray(other, dtype=np.float32)
-                    if f.ndim not in (2, 3) or f.size != f.shape[0] * 9:
-                        raise BvhError("other must have dtype TRIANGLE or shape (m, 9) / (m, 3, 3)")
-                    other, tri_format = f.reshape(-1, 9), TRI_PACKED36
-                other, n, own = _uploaded(ctx, other)
-            elif other is None and vertices is None and indices is None:
-                raise BvhError("another mesh is required (only self_pairs=True goes without)")
-            elif n is None:
-                stride = {TRI_PADDED64: 64, TRI_PACKED36: 36}.get(tri_format)
-                n = other.nbytes // stride if isinstance(other, DeviceBuffer) and stride else (indices.nbytes // 12 if isinstance(indices, DeviceBuffer) else None)
-                if n is None:
-                    raise BvhError("n is required for a device mesh")
+            other, tri_format, n, own = _as_mesh(ctx, other, tri_format, vertices, indices, n, "self_pairs=True")
             if n == 0:                                    # no queries: the empty answer, without a call
                 return _no_queries(False, np.uint32)
             qin = _build_input(tri_format, other, vertices, indices, n_vertices)
@@ -1472,6 +1484,7 @@ class Scene:
         ptr, n, dev = self._instances(instances)
         _check(lib().bvh_scene_build(self.handle, int(algo), arr, len(pairs), ptr, n, dev, C.byref(self.timings)), "bvh_scene_build")
         self.n_instances = n
+        self._max_leaves = max((int(d.tree.n_leaves) for d, _ in pairs), default=0)       # (intersect_tris(instance=k): enough rows for any BLAS)
         return self
 
     def update(self, instances) -> "Scene":
@@ -1585,6 +1598,40 @@ class Scene:
         self._sync_blas()
         return _count_fill(self.ctx, lambda off, out, cap, tot: lib().bvh_scene_overlap(self.handle, _ptr(boxes), n, flags, off, out, cap, tot), n,
                            INSTANCE_PRIM, count_only, capacity, "bvh_scene_overlap", own)
+
+    def intersect_tris(self, other=None, instance: int | None = None, sorted: bool = True, count_only: bool = False, capacity: int | None = None,
+                       tri_format: int = TRI_PADDED64, vertices=None, indices=None, n_vertices: int = 0, n: int | None = None):
+        """bvh_scene_intersect_tris: every (instance, triangle) pair whose world triangle each query triangle properly crosses.  Either ``other``, a mesh in
+        WORLD space as the builders' intersect_tris takes it — a host TRIANGLE array, a host (m, 9) or (m, 3, 3) float array (uploaded as TRI_PACKED36), or a
+        device buffer of records in ``tri_format`` (DeviceBuffer / int address, with ``n``); ``vertices`` / ``indices`` / ``n_vertices`` / ``n`` name a device
+        TRI_INDEXED mesh instead — or ``instance=k`` (BVH_SCENE_TRIS_INSTANCE): the rows are the world triangles of instance k's BLAS, instance k itself is
+        skipped, and the BLAS is looked up on the device; the answer then has ``n`` rows, those at or beyond the instance's n_leaves empty.  The default
+        ``n`` is an UPPER BOUND, not the instance's own count: the largest n_leaves among the BLASes as ``build`` recorded them (the host does not know which
+        BLAS a device-resident instance record names), so rows are launched, and offsets returned, for the largest BLAS; pass ``n`` to cut that.  The
+        scene copies each BLAS's n_leaves when it is built, so a BLAS rebuilt with another triangle count needs a new ``build`` in any case.  Returns host arrays (offsets u32[n + 1], records INSTANCE_PRIM[total]): query i's records are
+        records[offsets[i]:offsets[i + 1]], in ascending (instance, prim) order when ``sorted`` (BVH_SCENE_TRIS_SORTED; quadratic in a slice's length), in no
+        particular order otherwise.  ``count_only`` returns offsets alone.  ``capacity`` None: a count-only call first, then a call with the exact capacity;
+        a given capacity that is too small is re-allocated with the total the call reported and the call repeated once."""
+        own, qin = None, None
+        if instance is not None:
+            if other is not None or vertices is not None or indices is not None:
+                raise BvhError("instance=k takes no other mesh")
+            mode, k = SCENE_TRIS_INSTANCE, int(instance)
+            if not 0 <= k < self.n_instances:
+                raise BvhError(f"instance {k} of a scene of {self.n_instances}")
+            n = int(n) if n is not None else getattr(self, "_max_leaves", 0)
+        else:
+            mode, k = SCENE_TRIS_QUERY, 0
+            other, tri_format, n, own = _as_mesh(self.ctx, other, tri_format, vertices, indices, n, "instance=k")
+        if n == 0:                                        # no queries: the empty answer, without a call
+            return _no_queries(count_only, INSTANCE_PRIM)
+        if instance is None:
+            qin = _build_input(tri_format, other, vertices, indices, n_vertices)
+        flags = SCENE_TRIS_SORTED if sorted else 0
+        self._sync_blas()
+        return _count_fill(self.ctx, lambda off, out, cap, tot: lib().bvh_scene_intersect_tris(self.handle, _ref(qin), n, mode, k, flags, off, out, cap, tot), n,
+                           INSTANCE_PRIM, count_only, capacity, "bvh_scene_intersect_tris", own)
+
     def tlas(self) -> Result:
         r = Result()
         _check(lib().bvh_scene_tlas(self.handle, C.byref(r)), "bvh_scene_tlas")

@@ -323,6 +323,13 @@ void launch_scene_radius_fill(hipStream_t s, int sorted, const SceneQuery& q, co
 // once unless *h.total <= h.capacity and *h.total < 2^32; query i's records go to hits[offsets[i] ..], in ascending (instance, prim) order when sorted != 0
 void launch_scene_overlap_count(hipStream_t s, const SceneQuery& q, const SceneHits& h, uint64_t* d_sums, uint64_t* d_total);
 void launch_scene_overlap_fill(hipStream_t s, int sorted, const SceneQuery& q, const SceneHits& h);
+// bvh_scene_intersect_tris (scene_tris.hip): the same two calls over query triangles (q.rays is unused), with hits = bvh_instance_prim[capacity].  SceneTris is
+// the query side: the caller's world-space mesh (mode BVH_SCENE_TRIS_QUERY) or the instance whose world triangles ask (BVH_SCENE_TRIS_INSTANCE; queries unused).
+// k_scene_tris_count + k_scene_tris_deep + launch_overlap_scan; launch_scene_tris_fill: k_scene_tris_fill + k_scene_tris_deep, which return at once unless
+// *h.total <= h.capacity and *h.total < 2^32; query i's records go to hits[offsets[i] ..], in ascending (instance, prim) order when sorted != 0
+struct SceneTris { TrisMesh queries; int mode; uint32_t query_instance; };
+void launch_scene_tris_count(hipStream_t s, const SceneQuery& q, const SceneHits& h, const SceneTris& t, uint64_t* d_sums, uint64_t* d_total);
+void launch_scene_tris_fill(hipStream_t s, int sorted, const SceneQuery& q, const SceneHits& h, const SceneTris& t);
 
 // ---- BVH2 -> BVH4 collapse (collapse.hip)
 constexpr int COLLAPSE_MAX_BATCH = 64;                       // levels per batch of launches (one counter word per level)
@@ -352,6 +359,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_tris(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

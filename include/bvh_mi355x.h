@@ -890,7 +890,58 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  *   errors enqueue and write nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene; NULL d_boxes or d_offsets; a flag bit other than
  *     BVH_SCENE_OVERLAP_SORTED; n_boxes >= 2^30; d_offsets or d_prims (capacity records, clamped to 2^32 - 1) overlapping d_boxes or each other.
  *   n_boxes == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
- *   bvh_ctx_kernel_times reports k_scene_overlap_count, k_scene_overlap_fill, k_scene_overlap_deep (after each pass) and k_overlap_scan. */
+ *   bvh_ctx_kernel_times reports k_scene_overlap_count, k_scene_overlap_fill, k_scene_overlap_deep (after each pass) and k_overlap_scan.
+ * Crossing triangle pairs: bvh_scene_intersect_tris is bvh_intersect_tris on a scene — which triangles of which active instances does each query triangle
+ * properly cross?  Collision between the rigid bodies a scene models, without flattening it and after bvh_scene_update alone.  bvh_scene_overlap's two-level
+ * broad phase and bvh_intersect_tris's exact narrow phase in one walk; like both it is exact on EVERY query (tests/test_scene_intersect_tris.py restates the
+ * contract in numpy).
+ *   tree-side triangle (k, j): the WORLD TRIANGLE of primitive j of instance k's BLAS, bvh_scene_closest_point's: with m_rc = object_to_world[4r + c],
+ *     V.r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3 for each of the three vertices (x, y, z), in f32 without contraction, in exactly this order.  It is a value
+ *     that depends on the instance record and the BLAS triangle alone, not on the walk.
+ *   query triangle i: BVH_SCENE_TRIS_QUERY — triangle i of `queries`, n_queries triangles already in world space, device pointers, any bvh_tri_format
+ *     (morton_bits is ignored); query_instance must be 0.  BVH_SCENE_TRIS_INSTANCE — `queries` must be NULL and the rows are the triangles of instance
+ *     query_instance: if i < n_leaves of that instance's BLAS, query i is the world triangle (query_instance, i); a row at or beyond n_leaves has an empty
+ *     slice; an inactive query instance gives all-empty slices.  The device reads the BLAS index from the scene's instance array: there is no host read-back
+ *     and the call stays asynchronous, also after a bvh_scene_update from device memory.  Instance query_instance itself is skipped BY INDEX; a second
+ *     instance of the same BLAS is a different instance and answers.  As for BVH_TRIS_SELF the call reads triangle i of the BLAS's triangle array for every
+ *     i < n_leaves, so that array must hold n_leaves triangles: this mode is NOT usable on a BLAS over bvh_split_refs references relabelled by
+ *     bvh_remap_leaves, which the call cannot check.
+ *   answer: pair (i; k, j) is reported iff (a) instance k is active (and, in INSTANCE mode, k != query_instance), (b) primitive j's leaf box b is valid on
+ *     the OBJECT box, as for bvh_scene_overlap, (c) box_overlap(B(i), mapped(M_k, b)), where B(i) is stage E's box of query triangle i's three vertices, as in
+ *     bvh_intersect_tris (clamps against the reset box included), and mapped is bvh_scene_overlap's expression above, and (d) crosses(query_i, worldtri(k, j)),
+ *     bvh_intersect_tris's predicate word for word: IEEE f64 on the f32 world coordinates widened exactly, strict comparisons, proper() on both triangles.
+ *     Compressed-row form: d_prims[d_offsets[i] .. d_offsets[i+1]) is query i's slice of bvh_instance_prim {prim_idx, instance_idx} records, d_offsets[0] = 0,
+ *     d_offsets[n_queries] = the total.  Each pair appears at most once per slice.  There are no miss records: an empty slice crosses nothing.  With
+ *     d_prims == NULL the call only counts.
+ *   order inside a slice: without BVH_SCENE_TRIS_SORTED unspecified, but the same call on the same arrays gives the same bytes.  With BVH_SCENE_TRIS_SORTED
+ *     each slice is ascending in (instance_idx, prim_idx); the whole d_prims array then depends on none of the top-level builder, the BLAS builders, the
+ *     layouts, the formats, the traversal order.  Any other flag bit is an error.  The sorted insertion is quadratic in the slice's length.
+ *   exactness: the set is exact for EVERY query — there is no well-conditioned share — whenever every mapped value and every world coordinate is finite, every
+ *     internal box of every BLAS contains its children's boxes, and each leaf box is stage E's box of the BLAS triangle passed for it (true of a build, and
+ *     of a refit with the same triangles).  The argument: (1) if a vertex v lies in an object box {lo, hi}, its world vertex lies in
+ *     mapped(M, {lo, hi}) as values — each product m_rc * v.c lies between fminf and fmaxf of m_rc * lo.c and m_rc * hi.c because rounded multiplication by a
+ *     fixed factor is monotone, and the three rounded sums and the translation are added in the same association in V.r and in min.r / max.r, and rounded
+ *     addition is monotone; (2) stage E's leaf box contains its triangle's vertices (its clamps against the reset box leave every finite value as it is), so the mapped leaf box contains the world triangle; (3) two triangles
+ *     that cross share a point, which lies in B(i) and in the world triangle's box, so B(i) overlaps the mapped leaf box; (4) bvh_scene_overlap's argument
+ *     carries the pair up through the BLAS, the instance's world box and the top-level tree.  When a premise fails, every reported pair still passes its own
+ *     four tests and the slice is a subset of the true set.
+ *   relation to the other queries: with one identity instance, BVH_SCENE_TRIS_QUERY returns bvh_intersect_tris's prim sets on the BLAS
+ *     (((1 x + 0 y) + 0 z) + 0 == x as a value).  Slice i's (instance, prim) pairs are a subset of bvh_scene_overlap's slice for the box B(i).  crosses() is
+ *     symmetric, so (l, j) is in row i of INSTANCE(k) iff (k, i) is in row j of INSTANCE(l).
+ *   passes, capacity, total_out, saturation, asynchrony, scratch words: exactly bvh_scene_overlap's — the call always counts and scans; the fill decides ON
+ *     THE DEVICE whether it runs (d_prims != NULL, total <= capacity and total < 2^32); a skipped fill leaves d_prims untouched and d_offsets complete;
+ *     total_out != NULL is the only host wait; a total of 2^32 or more saturates d_offsets at 0xFFFFFFFF and returns BVH_E_TOO_LARGE when total_out was given
+ *     (with *total_out set); d_prims is never written outside query i's slice nor past the total; the per-query counter saturates at 0xFFFFFFFD; a
+ *     one-instance scene on a fresh ctx reserves the smallest arena at the first call.
+ *   no depth limit at either level: a query whose short stack would overflow is finished by a stackless pass through the plans the scene owns.  Both passes
+ *     test the same boxes and the same triangles, so count and fill agree on every query's set whichever pass served it.
+ *   errors enqueue and write nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene; NULL d_offsets; a flag bit other than BVH_SCENE_TRIS_SORTED;
+ *     n_queries >= 2^30; mode not 0 or 1; NULL queries with BVH_SCENE_TRIS_QUERY; queries given with BVH_SCENE_TRIS_INSTANCE; query_instance >= n_instances
+ *     with BVH_SCENE_TRIS_INSTANCE, query_instance != 0 with BVH_SCENE_TRIS_QUERY; a format error in queries (an unknown tri_format, a NULL or — for
+ *     PACKED36 — misaligned d_tris, INDEXED with a NULL vertex or index pointer or n_vertices == 0); d_offsets or d_prims (capacity records, clamped to
+ *     2^32 - 1) overlapping each other or the query mesh's triangle, vertex or index array.
+ *   n_queries == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
+ *   bvh_ctx_kernel_times reports k_scene_tris_count, k_scene_tris_fill, k_scene_tris_deep (after each pass) and k_overlap_scan. */
 typedef struct { bvh_result tree; bvh_build_input tris; } bvh_blas;   /* tris.tri_format PADDED64 with d_tris NULL: tree.d_tris is Triangle[n_leaves] */
 typedef struct bvh_scene bvh_scene;
 int  bvh_scene_create(bvh_ctx* ctx, bvh_scene** out);
@@ -912,6 +963,13 @@ int  bvh_scene_radius_search(bvh_scene* scene, const bvh_point_query* d_points, 
 int  bvh_scene_overlap(bvh_scene* scene, const bvh_aabb* d_boxes, uint32_t n_boxes, uint32_t flags /* 0 or BVH_SCENE_OVERLAP_SORTED */,
                        uint32_t* d_offsets /* u32[n_boxes + 1], device */, bvh_instance_prim* d_prims /* [capacity], device, or NULL: count only */,
                        uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+typedef enum { BVH_SCENE_TRIS_QUERY = 0, BVH_SCENE_TRIS_INSTANCE = 1 } bvh_scene_tris_mode;
+#define BVH_SCENE_TRIS_SORTED 1u
+int  bvh_scene_intersect_tris(bvh_scene* scene, const bvh_build_input* queries /* world-space mesh, device, any bvh_tri_format; NULL with BVH_SCENE_TRIS_INSTANCE */,
+                              uint32_t n_queries, int mode /* bvh_scene_tris_mode */, uint32_t query_instance /* BVH_SCENE_TRIS_INSTANCE only, else 0 */,
+                              uint32_t flags /* 0 or BVH_SCENE_TRIS_SORTED */, uint32_t* d_offsets /* u32[n_queries + 1], device */,
+                              bvh_instance_prim* d_prims /* [capacity], device, or NULL: count only */, uint64_t capacity,
+                              uint64_t* total_out /* host, may be NULL */);
 int  bvh_scene_tlas(const bvh_scene* scene, bvh_result* out);
 
 /* ---- stage-level entry points (one per reference kernel / library call on the path) -------------------------- */
