@@ -80,7 +80,7 @@ EXPORTS = [
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
-    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap", "bvh_scene_intersect_tris",
+    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap", "bvh_scene_intersect_tris", "bvh_scene_collide",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
@@ -127,6 +127,7 @@ RADIUS_SORTED = 1                    # BVH_RADIUS_SORTED (bvh_radius_search's an
 SCENE_OVERLAP_SORTED = 1             # BVH_SCENE_OVERLAP_SORTED (bvh_scene_overlap's flag)
 SCENE_TRIS_QUERY, SCENE_TRIS_INSTANCE = 0, 1   # bvh_scene_tris_mode (bvh_scene_intersect_tris)
 SCENE_TRIS_SORTED = 1                # BVH_SCENE_TRIS_SORTED (bvh_scene_intersect_tris's flag)
+SCENE_COLLIDE_SORTED, SCENE_COLLIDE_BOTH = 1, 2   # bvh_scene_collide's flags
 SPLIT_MAX_DEPTH = 16                 # BVH_SPLIT_MAX_DEPTH (bvh_split_refs)
 ABI_VERSION = 4                      # BVH_ABI_VERSION of include/bvh_mi355x.h this binding was written against
 # bvh_option (bvh_ctx_set_option) and the names this harness accepts for the values
@@ -242,6 +243,7 @@ def lib() -> C.CDLL:
         "bvh_scene_radius_search": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_scene_overlap": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_scene_intersect_tris": ([vp, C.POINTER(BuildInput), u32, i32, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_scene_collide": ([vp, u32, vp, u32, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)], i32),
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
@@ -1485,6 +1487,7 @@ class Scene:
         _check(lib().bvh_scene_build(self.handle, int(algo), arr, len(pairs), ptr, n, dev, C.byref(self.timings)), "bvh_scene_build")
         self.n_instances = n
         self._max_leaves = max((int(d.tree.n_leaves) for d, _ in pairs), default=0)       # (intersect_tris(instance=k): enough rows for any BLAS)
+        self._blas_leaves = np.array([int(d.tree.n_leaves) for d, _ in pairs], dtype=np.int64)          # (collide: the rows of a host instance array)
         return self
 
     def update(self, instances) -> "Scene":
@@ -1505,8 +1508,10 @@ class Scene:
             if instances.dtype != INSTANCE:
                 raise BvhError("instances must have dtype INSTANCE (64-byte records)")
             self._host = np.ascontiguousarray(instances)
+            self._host_current = True
             return self._host.ctypes.data, len(self._host), 0
         buf, n = instances
+        self._host_current = False                        # (the instance records are the device's: collide cannot count their rows)
         return _ptr(buf), int(n), 1
 
     def intersect(self, rays, query="closest", n_rays: int | None = None) -> np.ndarray:
@@ -1631,6 +1636,42 @@ class Scene:
         self._sync_blas()
         return _count_fill(self.ctx, lambda off, out, cap, tot: lib().bvh_scene_intersect_tris(self.handle, _ref(qin), n, mode, k, flags, off, out, cap, tot), n,
                            INSTANCE_PRIM, count_only, capacity, "bvh_scene_intersect_tris", own)
+
+    def collide(self, both: bool = False, sorted: bool = True, count_only: bool = False, capacity: int | None = None, row_capacity: int | None = None):
+        """bvh_scene_collide: the crossing triangle pairs of all instances at once.  The rows are the triangles of all active instances in instance order;
+        row r with row_first[k] <= r < row_first[k + 1] is triangle r - row_first[k] of instance k, and row_first[n_instances] is the number of rows.  Returns
+        host arrays (row_first u32[n_instances + 1], offsets u32[row_capacity + 1], records INSTANCE_PRIM[total]): row r's partners {prim, instance} are
+        records[offsets[r]:offsets[r + 1]] — the triangles of HIGHER instances that it properly crosses, so that every unordered pair appears once, or with
+        ``both`` those of every other instance — in ascending (instance, prim) order when ``sorted`` (BVH_SCENE_COLLIDE_SORTED; quadratic in a slice's length),
+        in no particular order otherwise.  ``count_only`` returns (row_first, offsets).  ``row_capacity`` None: the number of rows, computed from the host
+        instance array the scene was last built or updated with; if that array lives on the device, the upper bound n_instances x the largest n_leaves among
+        the BLASes.  Either way the call is then made with an upper bound (the host does not decide which instances are active) and the offsets returned are cut
+        to the row_first[-1] rows that exist; a given ``row_capacity`` returns all its rows, those behind row_first[-1] empty, and one below the number of rows
+        raises BvhError (BVH_E_TOO_LARGE).  ``capacity`` as for intersect_tris."""
+        cut = row_capacity is None
+        if row_capacity is None:
+            host = getattr(self, "_host", None)
+            if host is not None and getattr(self, "_host_current", False):
+                bl = host["blas"].astype(np.int64)
+                ok = (bl >= 0) & (bl < len(self._blas_leaves))
+                row_capacity = int(self._blas_leaves[bl[ok]].sum())    # (an upper bound too: an instance may be inactive for its matrix alone)
+            else:
+                row_capacity = self.n_instances * getattr(self, "_max_leaves", 0)
+        rows = int(row_capacity)
+        flags = (SCENE_COLLIDE_SORTED if sorted else 0) | (SCENE_COLLIDE_BOTH if both else 0)
+        first = self.ctx.alloc((self.n_instances + 1) * 4)
+        n_rows = C.c_uint64()
+        self._sync_blas()
+        try:
+            got = _count_fill(self.ctx, lambda off, out, cap, tot: lib().bvh_scene_collide(self.handle, flags, first.ptr, rows, off, out, cap, C.byref(n_rows), tot),
+                              rows, INSTANCE_PRIM, count_only, capacity, "bvh_scene_collide")
+            row_first = first.download(np.uint32, self.n_instances + 1)
+        finally:
+            first.free()
+        off, recs = (got, None) if count_only else got
+        if cut:
+            off = off[: int(row_first[-1]) + 1]
+        return (row_first, off) if count_only else (row_first, off, recs)
 
     def tlas(self) -> Result:
         r = Result()

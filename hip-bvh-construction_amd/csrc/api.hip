@@ -214,7 +214,7 @@ void carve(bvh_ctx* c, char* base, uint32_t cap, size_t* total) {
     c->ploc.ids1 = k.take<u32>(n);
     c->ploc.status = k.take<u64>((size_t)PLOC_MAX_ITERS * ploc_chunks(cap));
     c->ploc.state = k.take<u32>(PLOC_STATE_WORDS);
-    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58..61] the query calls' words (overflow_words / total_word below)
+    c->small = k.take<u32>(64);            // [0] root, [1] hploc zero-parent, [8..9] f64 SAH / BVH4 cost, [10..11] u64 checksum, [16..31] camera, [32..47] transform, [48..57] Morton plan read-back, [58..63] the query calls' words (overflow_words / total_word / rows_word below)
     c->hploc.zero_parent = c->small + 1;
     c->overlap_sums = k.take<u64>(OVERLAP_SCAN_BLOCKS);
     *total = k.off;
@@ -223,6 +223,7 @@ void carve(bvh_ctx* c, char* base, uint32_t cap, size_t* total) {
 // shares the pinned pairs): calls on one stream are ordered, so a call's kernels and its read-back are done with the words before the next call's memset runs.
 inline u32* overflow_words(const bvh_ctx* c) { return c->small + 58; }                            // queries left to the stackless pass: [0] single pass / count pass, [1] fill pass
 inline u64* total_word(const bvh_ctx* c) { return reinterpret_cast<u64*>(c->small + 60); }        // the count pass's u64 total (small[60..61])
+inline u64* rows_word(const bvh_ctx* c) { return reinterpret_cast<u64*>(c->small + 62); }         // bvh_scene_collide's u64 n_rows (small[62..63]): it survives the count pass's scan, which writes total_word
 inline u32* total_pairs(const bvh_ctx* c) { return c->h_pinned + 8; }                             // {lo, ~lo, hi, ~hi} of a total read back: pinned words 8..11
 
 int ensure_capacity(bvh_ctx* c, uint32_t n) {
@@ -532,7 +533,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_scene_collide(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -1733,6 +1734,51 @@ int bvh_scene_intersect_tris(bvh_scene* sc, const bvh_build_input* queries, uint
         launch_scene_tris_count(s, q, h, st, sc->ctx->overlap_sums, total);
         if (d_prims) { q.overflow = overflow + 1; launch_scene_tris_fill(s, (flags & BVH_SCENE_TRIS_SORTED) ? 1 : 0, q, h, st); }
     });
+}
+
+// bvh_scene_intersect_tris's INSTANCE mode for every instance at once: the row table is made on the device (launch_scene_collide_rows) in front of
+// bvh_scene_overlap's tail over row_capacity rows; every argument is checked before anything is enqueued, so an error writes nothing.  rows_out and total_out are
+// the only waits
+int bvh_scene_collide(bvh_scene* sc, uint32_t flags, uint32_t* d_row_first, uint32_t row_capacity, uint32_t* d_offsets, bvh_instance_prim* d_prims,
+                      uint64_t capacity, uint64_t* rows_out, uint64_t* total_out) {
+    if (!sc || !d_row_first || !d_offsets || !sc->built) return BVH_E_INVALID_ARG;
+    if (flags & ~(BVH_SCENE_COLLIDE_SORTED | BVH_SCENE_COLLIDE_BOTH)) return BVH_E_INVALID_ARG;
+    if (row_capacity >= (1u << 30)) return BVH_E_INVALID_ARG;
+    const Range rs[3] = { Range(d_row_first, ((uint64_t)sc->n_inst + 1u) * sizeof(u32)), Range(d_offsets, ((uint64_t)row_capacity + 1u) * sizeof(u32)),
+                          fill_range(d_prims, capacity, sizeof(bvh_instance_prim)) };
+    if (!disjoint(rs, 3, 3)) return BVH_E_INVALID_ARG;        // the three caller arrays must not overlap
+    bvh_ctx* const c = sc->ctx;
+    int r;
+    // (a one-instance scene on a fresh ctx never made the arena, and rows_word points into it: the smallest one, before the word's address is taken)
+    if (!c->arena) { Bind b(c->device); r = ensure_capacity(c, 2); if (r) return r; }
+    const SceneCollide rows{ d_row_first, rows_word(c), (flags & BVH_SCENE_COLLIDE_BOTH) ? 1 : 0 };
+    if (row_capacity == 0u) {                                 // no rows to answer: the table all the same, d_offsets[0] = total = 0
+        Bind b(c->device);
+        Install install(c);
+        launch_scene_collide_rows(c->stream, scene_query(sc, nullptr, 0, nullptr, nullptr), rows, c->overlap_sums);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u32), c->stream));
+        install.mark();
+        if (total_out) *total_out = 0;
+        r = 0;
+    } else {
+        r = count_fill_tail(c, nullptr, row_capacity, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
+            SceneQuery q = scene_query(sc, nullptr, row_capacity, d_prims, overflow);
+            const SceneHits h{ d_offsets, d_prims, total, capacity };
+            launch_scene_collide_rows(s, q, rows, c->overlap_sums);
+            launch_scene_collide_count(s, q, h, rows, c->overlap_sums, total);
+            if (d_prims) { q.overflow = overflow + 1; launch_scene_collide_fill(s, (flags & BVH_SCENE_COLLIDE_SORTED) ? 1 : 0, q, h, rows); }
+        });
+        if (r && r != BVH_E_TOO_LARGE) return r;
+    }
+    if (rows_out) {                                           // the u64 n_rows comes back through total_pairs, as a total does
+        Bind b(c->device);
+        u32* const rb = total_pairs(c);
+        const int w = read_back(c, reinterpret_cast<const u32*>(rows.d_n_rows), 2, nullptr, 0, rb); if (w) return w;
+        *rows_out = (uint64_t)rb[0] | ((uint64_t)rb[2] << 32);
+        if (*rows_out > row_capacity) return BVH_E_TOO_LARGE;
+    }
+    return r;
 }
 
 int bvh_scene_tlas(const bvh_scene* sc, bvh_result* out) {

@@ -330,6 +330,17 @@ void launch_scene_overlap_fill(hipStream_t s, int sorted, const SceneQuery& q, c
 struct SceneTris { TrisMesh queries; int mode; uint32_t query_instance; };
 void launch_scene_tris_count(hipStream_t s, const SceneQuery& q, const SceneHits& h, const SceneTris& t, uint64_t* d_sums, uint64_t* d_total);
 void launch_scene_tris_fill(hipStream_t s, int sorted, const SceneQuery& q, const SceneHits& h, const SceneTris& t);
+// bvh_scene_collide (scene_collide.hip): every instance's triangles ask at once (q.rays is unused, q.n_rays = row_capacity), with hits = bvh_instance_prim[capacity].
+// SceneCollide is the row table: d_row_first = the caller's u32[n_inst + 1], d_n_rows = a scratch u64 of its own (it must survive the count pass's scan, which
+// writes the query total elsewhere), both = BVH_SCENE_COLLIDE_BOTH.  launch_scene_collide_rows: k_scene_collide_rows (one thread per instance: n_leaves of its
+// BLAS, 0 if inactive) + launch_overlap_scan over them, which leaves row_first and *d_n_rows.  launch_scene_collide_count: k_scene_collide_count +
+// k_scene_collide_deep + launch_overlap_scan; launch_scene_collide_fill: k_scene_collide_fill + k_scene_collide_deep, which return at once unless
+// *h.total <= h.capacity and *h.total < 2^32; row r's records go to hits[offsets[r] ..], in ascending (instance, prim) order when sorted != 0.  Every kernel of
+// the two passes answers "no records" when *d_n_rows > q.n_rays
+struct SceneCollide { uint32_t* d_row_first; uint64_t* d_n_rows; int both; };
+void launch_scene_collide_rows(hipStream_t s, const SceneQuery& q, const SceneCollide& c, uint64_t* d_sums);
+void launch_scene_collide_count(hipStream_t s, const SceneQuery& q, const SceneHits& h, const SceneCollide& c, uint64_t* d_sums, uint64_t* d_total);
+void launch_scene_collide_fill(hipStream_t s, int sorted, const SceneQuery& q, const SceneHits& h, const SceneCollide& c);
 
 // ---- BVH2 -> BVH4 collapse (collapse.hip)
 constexpr int COLLAPSE_MAX_BATCH = 64;                       // levels per batch of launches (one counter word per level)
@@ -359,6 +370,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_tris(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_tris(); void warm_scene_collide(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

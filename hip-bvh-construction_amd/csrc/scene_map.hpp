@@ -1,9 +1,11 @@
 // scene_map.hpp — what the set-valued scene queries that test MAPPED boxes share (scene_overlap.hip: bvh_scene_overlap; scene_tris.hip:
-// bvh_scene_intersect_tris): the forward matrix of the entered instance, the header's mapped box and the record sink.
+// bvh_scene_intersect_tris; scene_collide.hip: bvh_scene_collide): the forward matrix of the entered instance, the header's mapped box, the
+// record sink and, for the two crossing-pair files, the world triangle of an instance's primitive.
 //   mapped(M, {lo, hi}), row r:  a_c = m_rc * lo.c, b_c = m_rc * hi.c,  min.r = ((fminf(a_0, b_0) + fminf(a_1, b_1)) + fminf(a_2, b_2)) + m_r3,  max.r with fmaxf
 // in f32 without contraction (every file that includes this is built with -ffp-contract=off and without the SLP vectoriser, Makefile).
 #pragma once
 #include "query.hpp"
+#include "tri_cross.hpp"
 #include "kernels.hpp"
 
 namespace bvh {
@@ -57,6 +59,20 @@ __device__ __forceinline__ bool sov_enter_instance(const SceneQuery& a, u32 k, S
     M.r0 = mq[0]; M.r1 = mq[1]; M.r2 = mq[2];
     B = a.blas[bl];
     return true;
+}
+
+// V.r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3: the header's world vertex (xf_point's order on the rows held in registers)
+__device__ __forceinline__ QF3 st_world(const SOMat& M, QF3 v) {
+    return { ((M.r0.x * v.x + M.r0.y * v.y) + M.r0.z * v.z) + M.r0.w, ((M.r1.x * v.x + M.r1.y * v.y) + M.r1.z * v.z) + M.r1.w,
+             ((M.r2.x * v.x + M.r2.y * v.y) + M.r2.z * v.z) + M.r2.w };
+}
+
+// the world triangle of primitive prim (< B.n) of the instance whose matrix is M
+__device__ __forceinline__ void st_world_tri(const SceneBlas& B, const SOMat& M, u32 prim, QF3& y1, QF3& y2, QF3& y3) {
+    const TriSrc src{ B.tris, reinterpret_cast<const float*>(B.tris), reinterpret_cast<const u32*>(B.idx), B.nv };
+    QF3 v1, v2, v3;
+    tt_query_fetch((int)B.fmt, src, prim, v1, v2, v3);
+    y1 = st_world(M, v1); y2 = st_world(M, v2); y3 = st_world(M, v3);
 }
 
 } // namespace bvh

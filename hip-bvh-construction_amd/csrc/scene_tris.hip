@@ -31,20 +31,6 @@ namespace bvh {
 // the query side of a launch: the caller's mesh and its format (QUERY mode), or the instance whose triangles ask (INSTANCE mode)
 struct STQuery { TriSrc src; int fmt; u32 inst; };
 
-// V.r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3: the header's world vertex (xf_point's order on the rows held in registers)
-__device__ __forceinline__ QF3 st_world(const SOMat& M, QF3 v) {
-    return { ((M.r0.x * v.x + M.r0.y * v.y) + M.r0.z * v.z) + M.r0.w, ((M.r1.x * v.x + M.r1.y * v.y) + M.r1.z * v.z) + M.r1.w,
-             ((M.r2.x * v.x + M.r2.y * v.y) + M.r2.z * v.z) + M.r2.w };
-}
-
-// the world triangle of primitive prim (< B.n) of the instance whose matrix is M
-__device__ __forceinline__ void st_world_tri(const SceneBlas& B, const SOMat& M, u32 prim, QF3& y1, QF3& y2, QF3& y3) {
-    const TriSrc src{ B.tris, reinterpret_cast<const float*>(B.tris), reinterpret_cast<const u32*>(B.idx), B.nv };
-    QF3 v1, v2, v3;
-    tt_query_fetch((int)B.fmt, src, prim, v1, v2, v3);
-    y1 = st_world(M, v1); y2 = st_world(M, v2); y3 = st_world(M, v3);
-}
-
 // query triangle i; false: the row is empty (INSTANCE mode: an inactive or out-of-range query instance, a row at or beyond its BLAS's n)
 template <int MODE>
 __device__ __forceinline__ bool st_query(const SceneQuery& a, const STQuery& t, u32 i, QF3& x1, QF3& x2, QF3& x3) {

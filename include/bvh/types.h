@@ -9,7 +9,7 @@
  *   bvh_knn_hit 8 B (one entry of bvh_knn's lists and one record of bvh_radius_search's slices; both read bvh_point_query too); no counterpart
  *   bvh_instance_knn_hit 16 B (one entry of bvh_scene_knn's lists and one record of bvh_scene_radius_search's slices: bvh_knn_hit with the instance, padded to one
  *     16-byte store); no counterpart
- *   bvh_instance_prim 8 B (one record of bvh_scene_overlap's and bvh_scene_intersect_tris's slices: a primitive of an instance); no counterpart
+ *   bvh_instance_prim 8 B (one record of bvh_scene_overlap's, bvh_scene_intersect_tris's and bvh_scene_collide's slices: a primitive of an instance); no counterpart
  * Usable from C, C++ and HIP device code. */
 #ifndef BVH_TYPES_H
 #define BVH_TYPES_H
@@ -50,7 +50,7 @@ typedef struct { bvh_float3 point; float dist2; float u, v; uint32_t prim_idx, i
 /* one entry of a scene's k-nearest list (bvh_scene_knn) and one record of bvh_scene_radius_search's slices: the squared WORLD distance of instance
  * instance_idx's triangle prim_idx; reserved = 0 (an unused slot of a k-nearest list: {radius*radius, BVH_INVALID, BVH_INVALID, 0}; a slice has no unused slots) */
 typedef struct { float dist2; uint32_t prim_idx, instance_idx, reserved; } bvh_instance_knn_hit;
-/* one record of bvh_scene_overlap's and bvh_scene_intersect_tris's slices: triangle prim_idx of instance instance_idx (a slice has no unused slots) */
+/* one record of bvh_scene_overlap's, bvh_scene_intersect_tris's and bvh_scene_collide's slices: triangle prim_idx of instance instance_idx (a slice has no unused slots) */
 typedef struct { uint32_t prim_idx, instance_idx; } bvh_instance_prim;
 
 #ifdef __cplusplus

@@ -941,7 +941,43 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  *     PACKED36 — misaligned d_tris, INDEXED with a NULL vertex or index pointer or n_vertices == 0); d_offsets or d_prims (capacity records, clamped to
  *     2^32 - 1) overlapping each other or the query mesh's triangle, vertex or index array.
  *   n_queries == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
- *   bvh_ctx_kernel_times reports k_scene_tris_count, k_scene_tris_fill, k_scene_tris_deep (after each pass) and k_overlap_scan. */
+ *   bvh_ctx_kernel_times reports k_scene_tris_count, k_scene_tris_fill, k_scene_tris_deep (after each pass) and k_overlap_scan.
+ * All instances at once: bvh_scene_collide is BVH_SCENE_TRIS_INSTANCE asked for every instance in one call — the crossing triangle pairs between the bodies
+ * of a scene, each unordered pair once, without a loop over instances on the host and without the host knowing which BLAS an instance places
+ * (tests/test_scene_collide.py restates the contract in numpy).
+ *   rows: the triangles of all instances, in instance order.  d_row_first[k] is the exclusive sum of n_leaves(BLAS of instance j) over the ACTIVE instances
+ *     j < k — an inactive instance has no rows — and d_row_first[n_instances] = n_rows.  Row r with d_row_first[k] <= r < d_row_first[k+1] is query triangle
+ *     (k, r - d_row_first[k]): the world triangle of that primitive of instance k, defined word for word as in BVH_SCENE_TRIS_INSTANCE.  Rows at or beyond
+ *     n_rows, up to row_capacity, are empty.
+ *   the table is made ON THE DEVICE from the scene's own instance array: there is no read-back, it follows a bvh_scene_update from device memory (also one that
+ *     hands an instance another BLAS), and d_row_first is written on every successful call.  An n_rows of 2^32 or more saturates d_row_first at 0xFFFFFFFF.
+ *   answer: pair (k, i; l, j) is in row (k, i) iff instance l is active; l > k — or, with BVH_SCENE_COLLIDE_BOTH, l != k —; and bvh_scene_intersect_tris's
+ *     conditions (b), (c) and (d) hold unchanged: primitive j's leaf box b of instance l's BLAS is valid, box_overlap(B(k, i), mapped(M_l, b)), and
+ *     crosses(worldtri(k, i), worldtri(l, j)) in f64 on the f32 world triangles with proper() on both.  So by default every unordered pair of triangles from
+ *     two DIFFERENT instances appears exactly once, in the row of the lower instance; with BVH_SCENE_COLLIDE_BOTH every row holds all its partners.  Pairs
+ *     inside one instance are never reported (that is BVH_TRIS_SELF on the BLAS); a second instance of the same BLAS is another instance and answers.
+ *   output: compressed-row form over row_capacity rows: d_prims[d_offsets[r] .. d_offsets[r+1]) is row r's slice of bvh_instance_prim
+ *     {prim_idx = j, instance_idx = l} records, d_offsets[0] = 0, d_offsets[row_capacity] = the total.  Without BVH_SCENE_COLLIDE_SORTED the order inside a
+ *     slice is unspecified, but the same call on the same arrays gives the same bytes; with it each slice is ascending in (instance_idx, prim_idx), and the
+ *     arrays then depend on no builder, layout or format.  The sorted insertion is quadratic in the slice's length.  With d_prims == NULL the call only counts.
+ *   exactness: bvh_scene_intersect_tris's, on every row and under its premises (every mapped value and world coordinate finite, nested BLAS boxes, leaf boxes
+ *     that are stage E's boxes of their triangles).  Under them the box test removes no crossing pair in either direction and crosses() is symmetric, so
+ *     (1) the default answer is the BVH_SCENE_COLLIDE_BOTH answer filtered to instance_idx > k, (2) total(BOTH) == 2 * total(default), and (3) with
+ *     SORTED | BOTH the rows of instance k equal the first n_leaves slices of bvh_scene_intersect_tris(BVH_SCENE_TRIS_INSTANCE, k, SORTED) byte for byte.
+ *   too many rows: if n_rows > row_capacity nothing is walked, every offset is 0 and d_prims is untouched; d_row_first is still complete, so
+ *     d_row_first[n_instances] tells a device-side caller; if rows_out was given, *rows_out = n_rows and the call returns BVH_E_TOO_LARGE.
+ *   passes, capacity, total_out, saturation, scratch words, row_capacity == 0: exactly bvh_scene_overlap's over the row_capacity rows — count, scan, then a
+ *     fill that decides ON THE DEVICE whether it runs (d_prims != NULL, total <= capacity and total < 2^32); a skipped fill leaves d_prims untouched and
+ *     d_offsets complete; a total of 2^32 or more saturates d_offsets and returns BVH_E_TOO_LARGE when total_out was given.  rows_out and total_out are the
+ *     only host waits (an 8-byte read-back each).  row_capacity == 0 writes d_offsets[0] = 0, *total_out = 0 and the table.
+ *   like BVH_SCENE_TRIS_INSTANCE the call reads triangle i of each BLAS's triangle array for every i < n_leaves: it is NOT usable on a BLAS over
+ *     bvh_split_refs references relabelled by bvh_remap_leaves, which the call cannot check.
+ *   no depth limit at either level: a row whose short stack would overflow is finished by a stackless pass that tests the same boxes and triangles.
+ *   errors enqueue and write nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene; NULL d_row_first or NULL d_offsets; a flag bit other than
+ *     BVH_SCENE_COLLIDE_SORTED and BVH_SCENE_COLLIDE_BOTH; row_capacity >= 2^30; any two of d_row_first (n_instances + 1 words), d_offsets
+ *     (row_capacity + 1 words) and d_prims (capacity records, clamped to 2^32 - 1) overlapping.
+ *   bvh_ctx_kernel_times reports k_scene_collide_rows, k_scene_collide_count, k_scene_collide_fill, k_scene_collide_deep (after each pass) and
+ *     k_overlap_scan. */
 typedef struct { bvh_result tree; bvh_build_input tris; } bvh_blas;   /* tris.tri_format PADDED64 with d_tris NULL: tree.d_tris is Triangle[n_leaves] */
 typedef struct bvh_scene bvh_scene;
 int  bvh_scene_create(bvh_ctx* ctx, bvh_scene** out);
@@ -970,6 +1006,12 @@ int  bvh_scene_intersect_tris(bvh_scene* scene, const bvh_build_input* queries /
                               uint32_t flags /* 0 or BVH_SCENE_TRIS_SORTED */, uint32_t* d_offsets /* u32[n_queries + 1], device */,
                               bvh_instance_prim* d_prims /* [capacity], device, or NULL: count only */, uint64_t capacity,
                               uint64_t* total_out /* host, may be NULL */);
+#define BVH_SCENE_COLLIDE_SORTED 1u
+#define BVH_SCENE_COLLIDE_BOTH   2u
+int  bvh_scene_collide(bvh_scene* scene, uint32_t flags /* BVH_SCENE_COLLIDE_SORTED | BVH_SCENE_COLLIDE_BOTH */,
+                       uint32_t* d_row_first /* u32[n_instances + 1], device */, uint32_t row_capacity,
+                       uint32_t* d_offsets /* u32[row_capacity + 1], device */, bvh_instance_prim* d_prims /* [capacity], device, or NULL: count only */,
+                       uint64_t capacity, uint64_t* rows_out /* host, may be NULL */, uint64_t* total_out /* host, may be NULL */);
 int  bvh_scene_tlas(const bvh_scene* scene, bvh_result* out);
 
 /* ---- stage-level entry points (one per reference kernel / library call on the path) -------------------------- */
