@@ -37,6 +37,8 @@ INSTANCE_POINT_HIT = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4
 POINT_QUERY = np.dtype([("point", "<f4", 3), ("radius", "<f4")])                                               # bvh_point_query (bvh_closest_point)
 POINT_HIT = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("reserved", "<u4")])   # bvh_point_hit
 WINDING_MOMENT = np.dtype([("a", "<f4", 3), ("area", "<f4"), ("p", "<f4", 3), ("r", "<f4")])                               # bvh_winding_moment (bvh_winding_prepare)
+WINDING_MAP = np.dtype([("c", "<f4", 9), ("smax", "<f4"), ("reserved", "<u4", 6)])                                          # bvh_winding_map (bvh_scene_winding_prepare)
+SCENE_WINDING_KEEP_BLAS = 1
 KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4")])                                                         # bvh_knn_hit (bvh_knn)
 KNN_MAX_K = 32
 INSTANCE_KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4")])         # bvh_instance_knn_hit (bvh_scene_knn, bvh_scene_radius_search)
@@ -83,6 +85,7 @@ EXPORTS = [
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap", "bvh_scene_intersect_tris", "bvh_scene_collide",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris",
+    "bvh_scene_winding_prepare", "bvh_scene_winding_number", "bvh_scene_winding_moments", "bvh_scene_winding_instances",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
 
@@ -244,6 +247,10 @@ def lib() -> C.CDLL:
         "bvh_scene_overlap": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_scene_intersect_tris": ([vp, C.POINTER(BuildInput), u32, i32, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_scene_collide": ([vp, u32, vp, u32, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)], i32),
+        "bvh_scene_winding_prepare": ([vp, u32], i32),
+        "bvh_scene_winding_number": ([vp, vp, u32, C.c_float, vp], i32),
+        "bvh_scene_winding_moments": ([vp, u32, C.POINTER(vp), C.POINTER(u32)], i32),
+        "bvh_scene_winding_instances": ([vp, C.POINTER(vp), C.POINTER(vp)], i32),
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
@@ -1486,6 +1493,7 @@ class Scene:
         ptr, n, dev = self._instances(instances)
         _check(lib().bvh_scene_build(self.handle, int(algo), arr, len(pairs), ptr, n, dev, C.byref(self.timings)), "bvh_scene_build")
         self.n_instances = n
+        self._winding_ready = False                       # (the build discarded the winding moments)
         self._max_leaves = max((int(d.tree.n_leaves) for d, _ in pairs), default=0)       # (intersect_tris(instance=k): enough rows for any BLAS)
         self._blas_leaves = np.array([int(d.tree.n_leaves) for d, _ in pairs], dtype=np.int64)          # (collide: the rows of a host instance array)
         return self
@@ -1496,6 +1504,7 @@ class Scene:
             raise BvhError(f"update with {n} instances of a scene built with {self.n_instances}")
         self._sync_blas()                                 # (a BLAS refit since the build must be complete: update re-reads the root boxes)
         _check(lib().bvh_scene_update(self.handle, ptr, dev, C.byref(self.timings)), "bvh_scene_update")
+        self._winding_ready = False                       # (the instance and top-level moments are stale)
         return self
 
     def _sync_blas(self) -> None:
@@ -1672,6 +1681,64 @@ class Scene:
         if cut:
             off = off[: int(row_first[-1]) + 1]
         return (row_first, off) if count_only else (row_first, off, recs)
+
+    def winding_prepare(self, keep_blas: bool = False) -> "Scene":
+        """bvh_scene_winding_prepare: the BLAS moments (all BLASes in two launches), the per-instance maps and moments and the top-level moments, in memory the
+        scene owns.  ``keep_blas`` (BVH_SCENE_WINDING_KEEP_BLAS) skips the BLAS moments when a prepare has succeeded since the last build: the cheap path
+        after update() when no BLAS was refit."""
+        self._sync_blas()
+        _check(lib().bvh_scene_winding_prepare(self.handle, SCENE_WINDING_KEEP_BLAS if keep_blas else 0), "bvh_scene_winding_prepare")
+        self._winding_ready = True
+        return self
+
+    def winding_moments(self, blas: int | None = None) -> np.ndarray:
+        """the prepared WINDING_MOMENT records of BLAS ``blas``, or of the top-level tree (None), downloaded"""
+        p, n = C.c_void_p(), C.c_uint32()
+        _check(lib().bvh_scene_winding_moments(self.handle, INVALID if blas is None else int(blas), C.byref(p), C.byref(n)), "bvh_scene_winding_moments")
+        out = np.empty(n.value, dtype=WINDING_MOMENT)
+        if n.value:
+            _check(lib().bvh_dev_download(self.ctx.handle, out.ctypes.data, p.value, out.nbytes), "bvh_dev_download")
+        return out
+
+    def winding_instances(self):
+        """(instance moments WINDING_MOMENT[n_instances], maps WINDING_MAP[n_instances]) as prepared, downloaded"""
+        pm, pc = C.c_void_p(), C.c_void_p()
+        _check(lib().bvh_scene_winding_instances(self.handle, C.byref(pm), C.byref(pc)), "bvh_scene_winding_instances")
+        mom, maps = np.empty(self.n_instances, dtype=WINDING_MOMENT), np.empty(self.n_instances, dtype=WINDING_MAP)
+        _check(lib().bvh_dev_download(self.ctx.handle, mom.ctypes.data, pm.value, mom.nbytes), "bvh_dev_download")
+        _check(lib().bvh_dev_download(self.ctx.handle, maps.ctypes.data, pc.value, maps.nbytes), "bvh_dev_download")
+        return mom, maps
+
+    def winding_number(self, points, beta: float = 2.0, n_points: int | None = None) -> np.ndarray:
+        """bvh_scene_winding_number: ``points`` as for the builders' winding_number (a host (n, 3) float array, a host POINT_QUERY array whose radius is ignored,
+        or a device buffer of POINT_QUERY records with ``n_points``) -> f32[n], summed over the world triangles of all active instances.  Prepares in full on
+        first use and after build() or update(); call winding_prepare(keep_blas=True) after an update() that only moved instances to skip the BLAS moments."""
+        if not getattr(self, "_winding_ready", False):
+            self.winding_prepare()
+        points, n_points, own = _as_points(self.ctx, points, None, n_points)      # (the radius is not read)
+        if n_points == 0:
+            return np.empty(0, dtype=np.float32)
+        w = self.ctx.alloc(n_points * 4)
+        self._sync_blas()
+        try:
+            _check(lib().bvh_scene_winding_number(self.handle, _ptr(points), n_points, float(beta), w.ptr), "bvh_scene_winding_number")
+            return w.download(np.float32, n_points)
+        finally:
+            w.free()
+            if own is not None:
+                own.free()
+
+    def signed_distance(self, points, beta: float = 2.0):
+        """-> (sd f32[n], hits INSTANCE_POINT_HIT[n]): closest_point's world distance sqrt(dist2) (unbounded radius), negated where winding_number > 0.5 (inside
+        the assembly).  ``points``: a host (n, 3) float array or POINT_QUERY records (their radius is replaced by +inf).  Plain composition of the two calls."""
+        if isinstance(points, np.ndarray) and points.dtype == POINT_QUERY:
+            points = np.ascontiguousarray(points["point"])
+        xyz = np.asarray(points, dtype=np.float32)
+        hits = self.closest_point(xyz)
+        w = self.winding_number(xyz, beta=beta)
+        with np.errstate(invalid="ignore"):
+            d = np.sqrt(hits["dist2"])
+            return np.where(w > np.float32(0.5), -d, d).astype(np.float32), hits
 
     def tlas(self) -> Result:
         r = Result()

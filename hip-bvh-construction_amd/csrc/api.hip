@@ -123,6 +123,12 @@ struct bvh_scene {
     u32* tparent = nullptr;            // [2n-1] top-level plan
     u32* flags = nullptr;              // [n] refit exchange words (all-INVALID, kept so)
     u32* overflow = nullptr;           // [1] rays left to the stackless pass
+    // winding numbers (bvh_scene_winding_prepare): an allocation of its own, made by the first prepare after a build and freed by the next build
+    std::vector<uint32_t> blas_n;      // the BLASes' leaf counts (host): the prefix table is made from them at prepare time
+    char* wmem = nullptr;
+    bvh::SceneWind wind{};
+    bool wind_blas_ok = false;         // the BLAS moments were made since the last bvh_scene_build
+    bool wind_ok = false;              // ... and the maps, instance moments and top-level moments since the last build or update
 };
 
 namespace {
@@ -533,7 +539,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_scene_collide(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_scene_collide(); warm_scene_winding(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -1520,7 +1526,7 @@ int bvh_scene_create(bvh_ctx* c, bvh_scene** out) {
 
 void bvh_scene_destroy(bvh_scene* sc) {
     if (!sc) return;
-    if (sc->mem) { Bind b(sc->ctx->device); hipStreamSynchronize(sc->ctx->stream); hipFree(sc->mem); }
+    if (sc->mem) { Bind b(sc->ctx->device); hipStreamSynchronize(sc->ctx->stream); hipFree(sc->mem); if (sc->wmem) hipFree(sc->wmem); }
     delete sc;
 }
 
@@ -1575,7 +1581,13 @@ int bvh_scene_build(bvh_scene* sc, bvh_algo algo, const bvh_blas* blas, uint32_t
     const size_t o_tnodes = take((2 * n - 1) * sizeof(bvh2_node)), o_tleaves = take(n * sizeof(bvh_primref)), o_tparent = take((2 * n - 1) * sizeof(u32));
     const size_t o_flags = take(n * sizeof(u32)), o_over = take(sizeof(u32)), o_plans = take(plan_words * sizeof(u32));
     sc->built = false;
-    if (sc->mem) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(sc->mem)); sc->mem = nullptr; }
+    sc->wind_blas_ok = sc->wind_ok = false;                      // (the winding moments describe the old BLAS set: discarded with it)
+    if (sc->mem) {
+        HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(sc->mem)); sc->mem = nullptr;
+        if (sc->wmem) { HIP_TRY(hipFree(sc->wmem)); sc->wmem = nullptr; }
+    }
+    sc->blas_n.resize(n_blas);
+    for (uint32_t k = 0; k < n_blas; ++k) sc->blas_n[k] = desc[k].n;
     HIP_TRY(hipMalloc(&sc->mem, off));
     char* m = sc->mem;
     sc->blas = reinterpret_cast<SceneBlas*>(m + o_blas); sc->inst_in = reinterpret_cast<bvh_instance*>(m + o_in); sc->inst = reinterpret_cast<SceneInst*>(m + o_inst);
@@ -1615,6 +1627,7 @@ int bvh_scene_update(bvh_scene* sc, const bvh_instance* instances, int on_device
     hipStream_t s = c->stream;
     const bool prof = c->profiling;
     if (prof) HIP_TRY(hipEventRecord(c->ev[0], s));
+    sc->wind_ok = false;                                         // (the maps, instance moments and top-level moments are stale; the BLAS moments are not)
     int r = scene_instances(sc, instances, on_device); if (r) return r;
     if (sc->n_inst >= 2) launch_refit_climb(s, sc->wbox, sc->tnodes, sc->tleaves, (int)sc->tlayout, sc->n_inst, sc->tparent, sc->flags);
     HIP_TRY(hipGetLastError());
@@ -1779,6 +1792,89 @@ int bvh_scene_collide(bvh_scene* sc, uint32_t flags, uint32_t* d_row_first, uint
         if (*rows_out > row_capacity) return BVH_E_TOO_LARGE;
     }
     return r;
+}
+
+// ---- winding numbers on scenes ------------------------------------------------------------------------------------------------------------------
+// the scene's winding memory: made by the first prepare after a build (the prefix table from the descriptors' leaf counts, the exchange words all-INVALID)
+static int scene_winding_alloc(bvh_scene* sc) {
+    const uint32_t n_blas = sc->n_blas;
+    std::vector<uint32_t> first(n_blas + 1);
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < n_blas; ++k) { first[k] = (uint32_t)total; total += sc->blas_n[k]; }
+    if (total >= (1ull << 32)) return BVH_E_TOO_LARGE;           // (one thread per leaf of all BLASes, 32-bit thread indices)
+    first[n_blas] = (uint32_t)total;
+    const size_t n = sc->n_inst;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
+    const size_t o_first = take((n_blas + 1) * sizeof(u32)), o_flags = take(total * sizeof(u32)), o_bmom = take((total - n_blas) * sizeof(bvh_winding_moment));
+    const size_t o_maps = take(n * sizeof(bvh_winding_map)), o_imom = take(n * sizeof(bvh_winding_moment)), o_tmom = take(n * sizeof(bvh_winding_moment));
+    char* m = nullptr;
+    HIP_TRY(hipMalloc(&m, off));
+    hipError_t e = hipMemcpy(m + o_first, first.data(), (n_blas + 1) * sizeof(u32), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(m + o_flags, 0xFF, total * sizeof(u32), sc->ctx->stream);
+    if (e != hipSuccess) { hipFree(m); return herr(e); }
+    sc->wmem = m;
+    SceneWind& w = sc->wind;
+    w.first = reinterpret_cast<const u32*>(m + o_first); w.flags = reinterpret_cast<u32*>(m + o_flags); w.bmom = reinterpret_cast<bvh_winding_moment*>(m + o_bmom);
+    w.maps = reinterpret_cast<bvh_winding_map*>(m + o_maps); w.imom = reinterpret_cast<bvh_winding_moment*>(m + o_imom);
+    w.tmom = reinterpret_cast<bvh_winding_moment*>(m + o_tmom);
+    w.n_blas = n_blas; w.total_leaves = (uint32_t)total;
+    return 0;
+}
+
+int bvh_scene_winding_prepare(bvh_scene* sc, uint32_t flags) {
+    if (!sc || !sc->built || (flags & ~(uint32_t)BVH_SCENE_WINDING_KEEP_BLAS)) return BVH_E_INVALID_ARG;
+    bvh_ctx* c = sc->ctx;
+    Bind b(c->device);
+    hipStream_t s = c->stream;
+    if (!sc->wmem) { const int r = scene_winding_alloc(sc); if (r) return r; }
+    Install install(c);
+    const bool keep = (flags & BVH_SCENE_WINDING_KEEP_BLAS) && sc->wind_blas_ok;
+    sc->wind_ok = false;
+    if (!keep) sc->wind_blas_ok = false;
+    const SceneQuery q = scene_query(sc, nullptr, 0, nullptr, nullptr);
+    if (!keep) launch_scene_winding_blas(s, q, sc->wind);
+    launch_scene_winding_top(s, q, sc->wind, sc->flags);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {                                       // (a refused launch may have left exchange words behind: all-INVALID again before the next climb)
+        hipMemsetAsync(sc->wind.flags, 0xFF, (size_t)sc->wind.total_leaves * sizeof(u32), s); hipMemsetAsync(sc->flags, 0xFF, (size_t)sc->n_inst * sizeof(u32), s);
+        return herr(e);
+    }
+    install.mark();
+    sc->wind_blas_ok = sc->wind_ok = true;
+    return 0;
+}
+
+// every argument is checked before anything is enqueued, so an error writes nothing; then bvh_scene_closest_point's tail
+int bvh_scene_winding_number(bvh_scene* sc, const bvh_point_query* d_points, uint32_t n_points, float beta, float* d_w) {
+    if (!sc || !sc->built || !sc->wind_ok || !d_points || !d_w || !(beta >= 0.0f)) return BVH_E_INVALID_ARG;     // (a NaN beta fails the comparison)
+    const Range pts(d_points, (uint64_t)n_points * sizeof(bvh_point_query)), out(d_w, (uint64_t)n_points * sizeof(float));
+    if (crosses(pts, out)) return BVH_E_INVALID_ARG;
+    if (n_points == 0) return 0;
+    return query_tail(sc->ctx, nullptr, sc->overflow, [&](hipStream_t s, u32* overflow) {
+        launch_scene_winding(s, scene_query(sc, d_points, n_points, d_w, overflow), sc->wind, beta);
+    });
+}
+
+int bvh_scene_winding_moments(const bvh_scene* sc, uint32_t blas, const bvh_winding_moment** d_moments, uint32_t* count) {
+    if (!sc || !sc->built || !d_moments || !count) return BVH_E_INVALID_ARG;
+    if (blas == BVH_INVALID) {
+        if (!sc->wind_ok) return BVH_E_INVALID_ARG;
+        *d_moments = sc->n_inst >= 2 ? sc->wind.tmom : nullptr; *count = sc->n_inst - 1;
+        return 0;
+    }
+    if (blas >= sc->n_blas || !sc->wind_blas_ok) return BVH_E_INVALID_ARG;
+    uint64_t first = 0;
+    for (uint32_t k = 0; k < blas; ++k) first += sc->blas_n[k];
+    *d_moments = sc->wind.bmom + (first - blas); *count = sc->blas_n[blas] - 1;
+    return 0;
+}
+
+int bvh_scene_winding_instances(const bvh_scene* sc, const bvh_winding_moment** d_inst_moments, const bvh_winding_map** d_maps) {
+    if (!sc || !sc->built || !sc->wind_ok || (!d_inst_moments && !d_maps)) return BVH_E_INVALID_ARG;
+    if (d_inst_moments) *d_inst_moments = sc->wind.imom;
+    if (d_maps) *d_maps = sc->wind.maps;
+    return 0;
 }
 
 int bvh_scene_tlas(const bvh_scene* sc, bvh_result* out) {

@@ -341,6 +341,20 @@ struct SceneCollide { uint32_t* d_row_first; uint64_t* d_n_rows; int both; };
 void launch_scene_collide_rows(hipStream_t s, const SceneQuery& q, const SceneCollide& c, uint64_t* d_sums);
 void launch_scene_collide_count(hipStream_t s, const SceneQuery& q, const SceneHits& h, const SceneCollide& c, uint64_t* d_sums, uint64_t* d_total);
 void launch_scene_collide_fill(hipStream_t s, int sorted, const SceneQuery& q, const SceneHits& h, const SceneCollide& c);
+// bvh_scene_winding_prepare / bvh_scene_winding_number (scene_winding.hip), beside a SceneQuery (rays = bvh_point_query[n_rays], hits = f32[n_rays]).  SceneWind is
+// the scene's winding memory: first = u32[n_blas + 1], the exclusive sum of the BLASes' leaf counts (BLAS b's exchange words are flags[first[b] ..
+// first[b + 1]), its n - 1 moments start at bmom + (first[b] - b)); flags all-INVALID before and left so; maps / imom per instance, tmom = the top-level
+// tree's n_inst - 1 records.  launch_scene_winding_blas: k_scene_winding_climb + k_scene_winding_finish over ALL BLASes (two launches whatever n_blas is).
+// launch_scene_winding_top: k_scene_winding_inst, then (n_inst >= 2) the same two kernels' top-level forms on the top-level plan and d_tflags (u32[n_inst],
+// all-INVALID before and left so).  launch_scene_winding: k_scene_winding (short stack shared by both levels; marks a query it leaves in hits[i]) +
+// k_scene_winding_deep (stackless, returns at once while *q.overflow == 0)
+struct SceneWind {
+    const uint32_t* first; uint32_t* flags; bvh_winding_moment* bmom; bvh_winding_map* maps; bvh_winding_moment* imom; bvh_winding_moment* tmom;
+    uint32_t n_blas, total_leaves;
+};
+void launch_scene_winding_blas(hipStream_t s, const SceneQuery& q, const SceneWind& w);
+void launch_scene_winding_top(hipStream_t s, const SceneQuery& q, const SceneWind& w, uint32_t* d_tflags);
+void launch_scene_winding(hipStream_t s, const SceneQuery& q, const SceneWind& w, float beta);
 
 // ---- BVH2 -> BVH4 collapse (collapse.hip)
 constexpr int COLLAPSE_MAX_BATCH = 64;                       // levels per batch of launches (one counter word per level)
@@ -370,6 +384,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_tris(); void warm_scene_collide(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_tris(); void warm_scene_collide(); void warm_scene_winding(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

@@ -6,6 +6,7 @@
  *   bvh_point_query 16 B (bvh_closest_point's input)      bvh_point_hit 32 B (its output); neither has a counterpart
  *   bvh_instance_point_hit 32 B (bvh_scene_closest_point's output: bvh_point_hit with the instance in its last word); no counterpart
  *   bvh_winding_moment 32 B (one internal node's record of bvh_winding_prepare, read by bvh_winding_number); no counterpart
+ *   bvh_winding_map 64 B (one instance's record of bvh_scene_winding_prepare: cofactor matrix and scale bound); no counterpart
  *   bvh_knn_hit 8 B (one entry of bvh_knn's lists and one record of bvh_radius_search's slices; both read bvh_point_query too); no counterpart
  *   bvh_instance_knn_hit 16 B (one entry of bvh_scene_knn's lists and one record of bvh_scene_radius_search's slices: bvh_knn_hit with the instance, padded to one
  *     16-byte store); no counterpart
@@ -39,6 +40,9 @@ typedef struct { bvh_float3 point; float dist2; float u, v; uint32_t prim_idx, r
 /* bvh_winding_prepare's record of one internal node: (ax, ay, az) = the sum of its triangles' area vectors, area = the sum of their areas, (px, py, pz) = their
  * area-weighted centroid (the centre of the node's box when area is 0 or non-finite), r = the distance from p to the farthest corner of the node's box */
 typedef struct { float ax, ay, az, area; float px, py, pz, r; } bvh_winding_moment;
+/* bvh_scene_winding_prepare's record of one instance with object_to_world [A | t]: c = the cofactor matrix of A, row-major (it maps area vectors:
+ * cross(A u, A v) = C (u x v)), smax = a bound on A's largest singular value; all zero for an inactive instance */
+typedef struct { float c[9]; float smax; uint32_t reserved[6]; } bvh_winding_map;
 /* one entry of a k-nearest list (bvh_knn) or of a radius search's slice (bvh_radius_search): the squared distance of triangle prim_idx's closest point (an
  * unused slot of a k-nearest list: {radius*radius, BVH_INVALID}; a slice has no unused slots) */
 typedef struct { float dist2; uint32_t prim_idx; } bvh_knn_hit;
@@ -63,6 +67,7 @@ static_assert(sizeof(bvh_hit) == 16, "bvh_hit is 16 bytes");
 static_assert(sizeof(bvh_point_query) == 16, "bvh_point_query is 16 bytes");
 static_assert(sizeof(bvh_point_hit) == 32, "bvh_point_hit is 32 bytes");
 static_assert(sizeof(bvh_winding_moment) == 32, "bvh_winding_moment is 32 bytes");
+static_assert(sizeof(bvh_winding_map) == 64, "bvh_winding_map is 64 bytes");
 static_assert(sizeof(bvh_knn_hit) == 8, "bvh_knn_hit is 8 bytes");
 static_assert(sizeof(bvh_instance) == 64, "bvh_instance is 64 bytes");
 static_assert(sizeof(bvh_instance_hit) == 32, "bvh_instance_hit is 32 bytes");

@@ -382,7 +382,7 @@ int  bvh_closest_point(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_inp
  * inside a closed, outward-oriented mesh, 0 outside, and a smooth function in between on meshes with holes, on triangle soups and on open scans.  Point-in-mesh
  * (w > 0.5), the SIGN of a distance field (bvh_closest_point's distance, negated where w > 0.5), voxelisation and fill, repair of open scans.  Evaluated
  * hierarchically as in Barill et al., "Fast winding numbers for soups and clouds" (2018): a far subtree contributes one dipole term, a near one is opened.
- * Flat trees only (no scenes).  Two calls: bvh_winding_prepare once per tree, bvh_winding_number per batch of points.
+ * On instanced scenes: bvh_scene_winding_number, below.  Two calls: bvh_winding_prepare once per tree, bvh_winding_number per batch of points.
  * tree / tris: exactly as bvh_closest_point — any bvh_result in either layout (a build's, a refit's, an optimised or a caller-filled one on the ctx's device),
  * triangles in any bvh_tri_format validated as by bvh_build_ex (NULL: tree->d_tris is read as Triangle[n_leaves]).  Nothing in the tree is written.  A
  * primitive or child index out of range is skipped (it contributes nothing); arrays that are not a tree end in finite time with unspecified answers.
@@ -977,7 +977,55 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  *     BVH_SCENE_COLLIDE_SORTED and BVH_SCENE_COLLIDE_BOTH; row_capacity >= 2^30; any two of d_row_first (n_instances + 1 words), d_offsets
  *     (row_capacity + 1 words) and d_prims (capacity records, clamped to 2^32 - 1) overlapping.
  *   bvh_ctx_kernel_times reports k_scene_collide_rows, k_scene_collide_count, k_scene_collide_fill, k_scene_collide_deep (after each pass) and
- *     k_overlap_scan. */
+ *     k_overlap_scan.
+ * Winding numbers: bvh_scene_winding_number is bvh_winding_number on a scene — inside / outside against an assembly of bodies, the sign for
+ * bvh_scene_closest_point's distance, voxelisation and point-in-union over thousands of bvh_build_many bodies — without flattening the scene.  Two calls:
+ * bvh_scene_winding_prepare after a build or an update, bvh_scene_winding_number per batch of points (tests/test_scene_winding.py restates both in numpy).
+ * All f32 without contraction in the stated order unless marked f64; dot and cross products as in the bvh_winding_number section.
+ *   world triangle of (instance k, primitive j): V_i = M_k v_i, V_i.r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3 — bvh_scene_closest_point's, in its order.
+ *   exact value: w(q) = the sum over the ACTIVE instances k and their primitives j of Omega(V1, V2, V3; q) / 4 pi, Omega being bvh_winding_number's leaf term
+ *     word for word on the world triangle and the world point.  The value is stated on world triangles because the solid angle of ONE triangle is not
+ *     invariant under a general 3x4 map; only the total over a closed surface is, so an object-space evaluation answers another function on open meshes under
+ *     shear or non-uniform scale.  A reflecting instance (det < 0) therefore contributes -1 inside: no sign rule is added.  Inactive instances
+ *     contribute nothing.  With beta = +inf the answer is this plain sum.
+ *   per instance (active; bvh_winding_map, written by prepare), with M = [A | t]: c = the cofactor matrix C of A, row-major: row 0 = {c00, c01, c02} of the
+ *     instance maths above, row 1 = {a02 a21 - a01 a22, a00 a22 - a02 a20, a01 a20 - a00 a21}, row 2 = {a01 a12 - a02 a11, a02 a10 - a00 a12,
+ *     a00 a11 - a01 a10}, in f64 from the f32 entries, each rounded once to f32.  It maps area vectors: cross(A u, A v) = C (u x v).
+ *     smax = (float)sqrt(lambda), lambda = max_i (|S_i0| + |S_i1|) + |S_i2| with S_ij = (a_i0 a_j0 + a_i1 a_j1) + a_i2 a_j2 in f64: a Gershgorin bound on the
+ *     largest singular value of A, with no guard factor on purpose (the identity gives exactly 1).  An inactive instance's record is all zero.
+ *   a BLAS node seen from the world: a BLAS node has the object record {A, area, p, r} — bvh_winding_prepare's, unchanged, made once per BLAS.  In instance k:
+ *     A_w.i = (C_i0 Ax + C_i1 Ay) + C_i2 Az; p_w = M_k p (the order above); r_w = smax * r; d = p_w - q; d2 = (dx*dx + dy*dy) + dz*dz; t = beta * r_w.  The
+ *     node is APPROXIMATED iff d2 > t * t (false on NaN); its term is dot(A_w, d) / ((FOURPI * d2) * sqrtf(d2)).  Every object point within r of p maps to
+ *     within sigma_max(A) r <= r_w of p_w, so the far-field condition of the flat walk holds in world space.
+ *   instance moment (a bvh_winding_moment, one per instance), from the BLAS root's record: A_k = C A in the order of A_w; area a_k = (smax * smax) * area;
+ *     p = c_k = M_k p; r_k = the distance from c_k to the farthest corner of the instance's world box, by bvh_winding_prepare's formula for r.  Inactive: all zero.
+ *   top-level moments: bvh_winding_moment[n_instances - 1], record i for top-level node i: bvh_winding_prepare's climb on the top-level tree with the leaf sums
+ *     {A_k, a_k, a_k * c_k} of the leaf's instance; an internal node's sums are left + right, following the tree, bit-reproducible; then p = M / a, or the
+ *     centre of the node's stored box if a is 0 or not finite, and r from the node's stored box, exactly as bvh_winding_prepare.
+ *   walk: with n_instances >= 2 the top-level root is always opened.  An internal top-level child follows bvh_winding_number's rule on its top-level record.
+ *     A top-level leaf child is instance k: it contributes its instance dipole (d = c_k - q with A_k and r_k) iff approximated, otherwise it is entered: its
+ *     BLAS root is opened, below it internal children use the world-mapped rule and leaf children add the world-triangle term.  With n_instances == 1 the
+ *     instance is always entered.  Children are taken left first.  The f32 terms go into one f64 sum carried across levels, stored as f32; a NaN answer is
+ *     stored as 0x7FC00000, a query with a NaN coordinate writes that NaN, the radius is ignored.
+ *   consequences: one identity instance opens exactly the nodes bvh_winding_number opens on the BLAS and adds bit-equal terms; any similarity transform gives
+ *     the flat answer at the mapped point, up to rounding.
+ *   bvh_scene_winding_prepare(scene, flags): the scene owns the memory (allocated by the first prepare after a build, outside the ctx's arena, freed by the
+ *     next build): the per-BLAS moments, one exchange word per BLAS leaf (kept all-INVALID), the per-instance maps, the instance moments and the top-level
+ *     moments.  The moments of ALL BLASes are made by one climb launch and one finish launch, whatever n_blas is (one thread per (BLAS, sorted leaf), the
+ *     BLAS found in a prefix table made from the descriptors): byte for byte bvh_winding_prepare's records of each BLAS.  BVH_SCENE_WINDING_KEEP_BLAS skips
+ *     them when a prepare has succeeded since the last bvh_scene_build: the cheap path after bvh_scene_update, which only moves instances.  A caller who
+ *     refits a BLAS prepares without the flag; the scene cannot detect a refit.  bvh_scene_build discards everything; bvh_scene_update makes the instance and
+ *     top-level part stale.  Asynchronous on the ctx's stream (the first prepare after a build allocates and copies the table, which blocks).  Errors
+ *     (BVH_E_INVALID_ARG): a NULL or unbuilt scene, a flag bit other than BVH_SCENE_WINDING_KEEP_BLAS; BVH_E_TOO_LARGE: 2^32 or more BLAS leaves in all.
+ *   bvh_scene_winding_number(scene, d_points, n_points, beta, d_w): asynchronous, no read-back, no depth limit at either level (queries whose short stack
+ *     would overflow are finished by a stackless pass through the top-level plan and the BLAS plans).  Returns BVH_E_INVALID_ARG and writes nothing for a
+ *     NULL or unbuilt scene, moments missing or stale (no prepare since the last build or update), NULL d_points or d_w, beta < 0 or NaN, overlapping
+ *     d_points / d_w ranges.  n_points == 0 returns 0 and touches nothing.  BLAS ordering as for bvh_scene_intersect.
+ *   accessors (read-only device pointers, valid until the next bvh_scene_build or bvh_scene_destroy; BVH_E_INVALID_ARG while the part asked for is missing or
+ *     stale): bvh_scene_winding_moments(scene, blas, ...) gives BLAS blas's n_leaves - 1 records or, with blas == BVH_INVALID, the top-level tree's
+ *     n_instances - 1 (NULL and 0 with one instance); bvh_scene_winding_instances gives the instance moments and the maps (either pointer may be NULL).
+ *   bvh_ctx_kernel_times reports k_scene_winding_climb and k_scene_winding_finish (both levels), k_scene_winding_inst, k_scene_winding and
+ *     k_scene_winding_deep. */
 typedef struct { bvh_result tree; bvh_build_input tris; } bvh_blas;   /* tris.tri_format PADDED64 with d_tris NULL: tree.d_tris is Triangle[n_leaves] */
 typedef struct bvh_scene bvh_scene;
 int  bvh_scene_create(bvh_ctx* ctx, bvh_scene** out);
@@ -1012,6 +1060,13 @@ int  bvh_scene_collide(bvh_scene* scene, uint32_t flags /* BVH_SCENE_COLLIDE_SOR
                        uint32_t* d_row_first /* u32[n_instances + 1], device */, uint32_t row_capacity,
                        uint32_t* d_offsets /* u32[row_capacity + 1], device */, bvh_instance_prim* d_prims /* [capacity], device, or NULL: count only */,
                        uint64_t capacity, uint64_t* rows_out /* host, may be NULL */, uint64_t* total_out /* host, may be NULL */);
+#define BVH_SCENE_WINDING_KEEP_BLAS 1u
+int  bvh_scene_winding_prepare(bvh_scene* scene, uint32_t flags /* 0 or BVH_SCENE_WINDING_KEEP_BLAS */);
+int  bvh_scene_winding_number(bvh_scene* scene, const bvh_point_query* d_points /* radius ignored */, uint32_t n_points, float beta,
+                              float* d_w /* f32[n_points], device */);
+int  bvh_scene_winding_moments(const bvh_scene* scene, uint32_t blas /* or BVH_INVALID: the top level */, const bvh_winding_moment** d_moments, uint32_t* count);
+int  bvh_scene_winding_instances(const bvh_scene* scene, const bvh_winding_moment** d_inst_moments /* [n_instances] */,
+                                 const bvh_winding_map** d_maps /* [n_instances] */);
 int  bvh_scene_tlas(const bvh_scene* scene, bvh_result* out);
 
 /* ---- stage-level entry points (one per reference kernel / library call on the path) -------------------------- */
