@@ -41,6 +41,7 @@ WINDING_MAP = np.dtype([("c", "<f4", 9), ("smax", "<f4"), ("reserved", "<u4", 6)
 SCENE_WINDING_KEEP_BLAS = 1
 KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4")])                                                         # bvh_knn_hit (bvh_knn)
 KNN_MAX_K = 32
+TRI_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("feature", "<u4"), ("reserved", "<u4")])                   # bvh_tri_hit (bvh_closest_tris)
 INSTANCE_KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4")])         # bvh_instance_knn_hit (bvh_scene_knn, bvh_scene_radius_search)
 INSTANCE_PRIM = np.dtype([("prim", "<u4"), ("instance", "<u4")])                                                   # bvh_instance_prim (bvh_scene_overlap)
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
@@ -84,7 +85,7 @@ EXPORTS = [
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap", "bvh_scene_intersect_tris", "bvh_scene_collide",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
-    "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris",
+    "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris", "bvh_closest_tris",
     "bvh_scene_winding_prepare", "bvh_scene_winding_number", "bvh_scene_winding_moments", "bvh_scene_winding_instances",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
@@ -255,6 +256,7 @@ def lib() -> C.CDLL:
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_intersect_tris": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(BuildInput), u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_closest_tris": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(BuildInput), u32, C.c_float, vp, i32], i32),
         "bvh_intersect_all": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_radius_search": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_winding_prepare": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp], i32),
@@ -1239,6 +1241,45 @@ class _Builder:
         res = C.byref(self.result)
         return _count_fill(ctx, lambda off, out, cap, tot: lib().bvh_intersect_tris(ctx.handle, res, _ref(tin), _ref(qin), n, mode, off, out, cap, tot), n,
                            np.uint32, False, max(int(capacity) if capacity is not None else n, 1), f"{ALGO_NAMES[self.ALGO]}::intersect_tris", own)
+    def closest_tris(self, other, radius=None, query="closest", tri_format: int = TRI_PADDED64, vertices=None, indices=None, n_vertices: int = 0,
+                     n: int | None = None, tree_tris=None, tree_vertices=None, tree_indices=None, tree_n_vertices: int = 0,
+                     tree_tri_format: int = TRI_PADDED64) -> np.ndarray:
+        """bvh_closest_tris on this builder's tree: the nearest tree triangle to each triangle of another mesh within ``radius`` (one bound for the call; None:
+        +inf), or with query "any" some tree triangle within it.  ``other`` as intersect_tris takes it: a host TRIANGLE array, a host (m, 9) or (m, 3, 3) float
+        array (uploaded as TRI_PACKED36), or a device buffer of records in ``tri_format`` (DeviceBuffer / int address, with ``n``); ``vertices`` / ``indices`` /
+        ``n_vertices`` / ``n`` name a device TRI_INDEXED mesh instead.  The tree's triangles as for intersect_tris (tree_*).  Returns a host TRI_HIT array:
+        {dist2, prim, feature, 0} per query triangle, a miss {radius * radius, INVALID, 0, 0}."""
+        if self._ctx is None:
+            raise BvhError("closest_tris needs a built tree")
+        ctx = self._ctx
+        q = _QUERY_IDS[query] if isinstance(query, str) else int(query)
+        other, tri_format, n, own = _as_mesh(ctx, other, tri_format, vertices, indices, n, "no call")
+        hits = None
+        try:
+            if n == 0:                                        # no queries: the empty answer, without a call
+                return np.zeros(0, dtype=TRI_HIT)
+            qin = _build_input(tri_format, other, vertices, indices, n_vertices)
+            tree_tris, tree_tri_format = self._own_tris(tree_tris, tree_vertices, tree_indices, tree_tri_format)
+            tin = _tri_input(tree_tris, tree_vertices, tree_indices, tree_n_vertices, tree_tri_format)
+            hits = ctx.alloc(n * TRI_HIT.itemsize)
+            _check(lib().bvh_closest_tris(ctx.handle, C.byref(self.result), _ref(tin), _ref(qin), n, float("inf") if radius is None else float(radius), hits.ptr, q),
+                   f"{ALGO_NAMES[self.ALGO]}::closest_tris")
+            return hits.download(TRI_HIT, n)
+        finally:
+            if hits is not None:
+                hits.free()
+            if own is not None:
+                own.free()
+    def distance_to(self, other, **mesh):
+        """-> (distance, query index, prim index): the distance between this builder's mesh and ``other`` (as closest_tris takes it, with its keyword
+        arguments) — sqrt of the smallest dist2 of one unbounded "closest" call, the query triangle that attains it (the lowest index on a tie) and its nearest
+        tree triangle; (inf, -1, -1) when nothing was found (no query triangles, or all of them with a NaN)"""
+        rec = self.closest_tris(other, radius=None, query="closest", **mesh)
+        idx = np.nonzero(rec["prim"] != INVALID)[0]
+        if len(idx) == 0:
+            return float("inf"), -1, -1
+        i = int(idx[np.argmin(rec["dist2"][idx])])              # (a hit's dist2 is never a NaN; argmin keeps the first of equal values)
+        return float(np.sqrt(np.float64(rec["dist2"][i]))), i, int(rec["prim"][i])
     def intersect_all(self, rays, sorted: bool = True, count_only: bool = False, capacity: int | None = None, tris=None, vertices=None, indices=None,
                       n_vertices: int = 0, tri_format: int = TRI_PADDED64, n: int | None = None):
         """bvh_intersect_all on this builder's tree: every accepted hit along each ray.  ``rays`` a host RAY array or a device buffer (DeviceBuffer / int

@@ -539,7 +539,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_scene_collide(); warm_scene_winding(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_scene_collide(); warm_scene_winding(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_closest_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -1145,6 +1145,32 @@ int bvh_intersect_tris(bvh_ctx* c, const bvh_result* tree, const bvh_build_input
         if (d_prims)
             launch_tris_fill(s, (int)tree->layout, mode, tm, qm, n_queries, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, d_prims, capacity, total,
                              overflow + 1, c->parent);
+    });
+}
+
+// ---- mesh-to-mesh distance (no counterpart in the reference) --------------------------------------------------------------------------------------
+// bvh_closest_point's checks (query_check: the hit array stands in for the query array, whose ranges are checked below) and tail, bvh_intersect_tris's
+// validation of the query mesh; every argument is checked before anything is enqueued, so an error writes nothing.  d_hits may overlap no array the call reads
+int bvh_closest_tris(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_build_input* queries, uint32_t n_queries, float radius,
+                     bvh_tri_hit* d_hits, int query) {
+    if (!queries || n_queries >= (1u << 30)) return BVH_E_INVALID_ARG;
+    bvh_build_input in;
+    int r = query_check(c, tree, tris, query, d_hits, 0, d_hits, 0, &in); if (r) return r;
+    if (stage_extents_valid(queries)) return BVH_E_INVALID_ARG;
+    const bvh_build_input qin = *queries;
+    {   // the answers against everything the call reads
+        Range rs[7] = { Range(d_hits, (uint64_t)n_queries * sizeof(bvh_tri_hit)) };
+        int k = 1 + tree_ranges(tree, rs + 1);
+        k += mesh_ranges(in, tree->n_leaves, rs + k);
+        k += mesh_ranges(qin, n_queries, rs + k);
+        if (!disjoint(rs, 1, k)) return BVH_E_INVALID_ARG;
+    }
+    if (n_queries == 0) return 0;
+    const TrisMesh tm{ (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices };
+    const TrisMesh qm{ (int)qin.tri_format, qin.d_tris, qin.d_vertices, qin.d_indices, qin.n_vertices };
+    return query_tail(c, tree, overflow_words(c), [&](hipStream_t s, u32* overflow) {
+        launch_closest_tris(s, (int)tree->layout, query, tm, qm, n_queries, radius, tree->d_nodes, tree->d_leaves, tree->n_leaves, tree->root, d_hits, overflow,
+                            c->parent);
     });
 }
 

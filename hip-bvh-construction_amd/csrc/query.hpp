@@ -1,4 +1,4 @@
-// query.hpp — device helpers shared by the query kernels (query.hip: bvh_intersect; scene.hip: bvh_scene_intersect; point_query.hip: bvh_closest_point): the
+// query.hpp — device helpers shared by the query kernels (query.hip: bvh_intersect; scene.hip: bvh_scene_intersect; point_query.hip: bvh_closest_point; closest_tris.hip: bvh_closest_tris): the
 // hit test, the closest-point formula, the conservative box tests, record / triangle / ray / point loads.  Compiled with -ffp-contract=off (Makefile): tri_hit is the reference's intersectTriangle operation for operation.
 #pragma once
 #include "bvh_mi355x.h"
@@ -132,6 +132,25 @@ __device__ __forceinline__ bool box_dist_pass(const Box& b, QF3 p, float best, f
     const float dx = fmaxf(fmaxf((b.lx - g) - p.x, p.x - (b.hx + g)), 0.0f);
     const float dy = fmaxf(fmaxf((b.ly - g) - p.y, p.y - (b.hy + g)), 0.0f);
     const float dz = fmaxf(fmaxf((b.lz - g) - p.z, p.z - (b.hz + g)), 0.0f);
+    const float lb = (dx * dx + dy * dy) + dz * dz;
+    lb_out = lb;
+    return lb * (1.0f - PQUERY_REL) <= best;
+}
+
+// a query box grown once for box_box_dist_pass: every plane moves out by QUERY_GROW * (the box's largest |coordinate|), as box_dist_pass grows a node box
+__device__ __forceinline__ Box box_grown(const Box& b) {
+    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz)));
+    return { b.lx - g, b.ly - g, b.lz - g, b.hx + g, b.hy + g, b.hz + g };
+}
+
+// box_dist_pass for a query that is itself a box (closest_tris.hip: bvh_closest_tris): qg = the query's box, already grown (box_grown); b grows
+// here.  The per-axis gap is the larger of the two one-sided gaps, or 0 where the intervals overlap; lb_out = the f32 sum of the squared gaps, for ordering.
+// fmaxf drops the NaN of a NaN or infinite plane (the axis then costs 0).  True iff the box may hold an accepted candidate
+__device__ __forceinline__ bool box_box_dist_pass(const Box& b, const Box& qg, float best, float& lb_out) {
+    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz)));
+    const float dx = fmaxf(fmaxf((b.lx - g) - qg.hx, qg.lx - (b.hx + g)), 0.0f);
+    const float dy = fmaxf(fmaxf((b.ly - g) - qg.hy, qg.ly - (b.hy + g)), 0.0f);
+    const float dz = fmaxf(fmaxf((b.lz - g) - qg.hz, qg.lz - (b.hz + g)), 0.0f);
     const float lb = (dx * dx + dy * dy) + dz * dz;
     lb_out = lb;
     return lb * (1.0f - PQUERY_REL) <= best;

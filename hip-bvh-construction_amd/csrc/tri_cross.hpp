@@ -1,5 +1,5 @@
 // tri_cross.hpp — the crossing predicate of bvh_intersect_tris (the header's contract), shared by intersect_tris.hip (tree-side triangles in
-// object space) and scene_tris.hip (tree-side triangles mapped to world space): IEEE f64 on the f32 coordinates widened exactly, no contraction
+// object space), scene_tris.hip (tree-side triangles mapped to world space) and closest_tris.hip (bvh_closest_tris's distance-0 case): IEEE f64 on the f32 coordinates widened exactly, no contraction
 // (-ffp-contract=off), no reassociation; strict comparisons only; both triangles must be proper (tt_proper).  The coordinates stay in f32 registers and are
 // widened where a difference is formed: two triangles held in f64 would be 36 more VGPRs for values that cost one v_cvt_f64_f32 each to remake.
 #pragma once

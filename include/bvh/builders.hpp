@@ -213,6 +213,14 @@ public:
               "closestPoint");
     }
 
+    // beyond the reference (bvh_closest_tris): the nearest triangle of this tree to each of the n triangles of `queries` (device pointers, any bvh_tri_format)
+    // within `radius` (one bound for the call; infinity: none), or any triangle within it, as one {dist2, prim, feature, 0} record per query; against the same
+    // tree and triangles as intersect
+    void closestTris(Context& context, const bvh_build_input* queries, u32 n, float radius, bvh_tri_hit* d_hits, bvh_query_kind kind) {
+        check(bvh_closest_tris(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, queries, n, radius, d_hits, static_cast<int>(kind)),
+              "closestTris");
+    }
+
     // beyond the reference (bvh_winding_prepare / bvh_winding_number): the generalized winding number of each point (1 inside a closed, outward-oriented mesh,
     // 0 outside), against the same tree and triangles as intersect.  d_moments: caller-owned bvh_winding_moment[n_leaves - 1], 16-byte aligned; prepare again
     // after a refit, an optimise or a rebuild.  The sign of a distance field: closestPoint's distance, negated where w > 0.5

@@ -8,6 +8,7 @@
  *   bvh_winding_moment 32 B (one internal node's record of bvh_winding_prepare, read by bvh_winding_number); no counterpart
  *   bvh_winding_map 64 B (one instance's record of bvh_scene_winding_prepare: cofactor matrix and scale bound); no counterpart
  *   bvh_knn_hit 8 B (one entry of bvh_knn's lists and one record of bvh_radius_search's slices; both read bvh_point_query too); no counterpart
+ *   bvh_tri_hit 16 B (bvh_closest_tris's output: the nearest tree triangle to a query triangle); no counterpart
  *   bvh_instance_knn_hit 16 B (one entry of bvh_scene_knn's lists and one record of bvh_scene_radius_search's slices: bvh_knn_hit with the instance, padded to one
  *     16-byte store); no counterpart
  *   bvh_instance_prim 8 B (one record of bvh_scene_overlap's, bvh_scene_intersect_tris's and bvh_scene_collide's slices: a primitive of an instance); no counterpart
@@ -46,6 +47,10 @@ typedef struct { float c[9]; float smax; uint32_t reserved[6]; } bvh_winding_map
 /* one entry of a k-nearest list (bvh_knn) or of a radius search's slice (bvh_radius_search): the squared distance of triangle prim_idx's closest point (an
  * unused slot of a k-nearest list: {radius*radius, BVH_INVALID}; a slice has no unused slots) */
 typedef struct { float dist2; uint32_t prim_idx; } bvh_knn_hit;
+/* bvh_closest_tris's answer to one query triangle: dist2 = the squared distance to tree triangle prim_idx, feature = which of the 16 terms of the header's
+ * dist2(X, Y) gave it (0..2: a query vertex against the tree triangle, 3..5: a tree vertex against the query triangle, 6 + 3*i + j: edge i of the query against
+ * edge j of the tree triangle, 15: a proper crossing); a miss: {radius*radius, BVH_INVALID, 0, 0} */
+typedef struct { float dist2; uint32_t prim_idx; uint32_t feature; uint32_t reserved; } bvh_tri_hit;
 /* object_to_world: row-major 3x4 matrix {m00 m01 m02 m03, m10 .. m13, m20 .. m23}; world = M * (object, 1).  blas: index into the scene's bottom-level table */
 typedef struct { float object_to_world[12]; uint32_t blas; uint32_t reserved[3]; } bvh_instance;
 typedef struct { float t, u, v; uint32_t prim_idx, instance_idx; uint32_t reserved[3]; } bvh_instance_hit;
@@ -69,6 +74,7 @@ static_assert(sizeof(bvh_point_hit) == 32, "bvh_point_hit is 32 bytes");
 static_assert(sizeof(bvh_winding_moment) == 32, "bvh_winding_moment is 32 bytes");
 static_assert(sizeof(bvh_winding_map) == 64, "bvh_winding_map is 64 bytes");
 static_assert(sizeof(bvh_knn_hit) == 8, "bvh_knn_hit is 8 bytes");
+static_assert(sizeof(bvh_tri_hit) == 16, "bvh_tri_hit is 16 bytes");
 static_assert(sizeof(bvh_instance) == 64, "bvh_instance is 64 bytes");
 static_assert(sizeof(bvh_instance_hit) == 32, "bvh_instance_hit is 32 bytes");
 static_assert(sizeof(bvh_instance_point_hit) == 32, "bvh_instance_point_hit is 32 bytes");

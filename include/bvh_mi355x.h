@@ -608,6 +608,66 @@ int  bvh_intersect_tris(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_in
                         uint32_t n_queries, int mode /* bvh_tris_mode */, uint32_t* d_offsets /* u32[n_queries + 1], device */,
                         uint32_t* d_prims /* u32[capacity], device, or NULL: count only */, uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
 
+/* ---- mesh-to-mesh distance (no counterpart in the reference) -----------------------------------------------------------------------------
+ * Which triangle of the tree is nearest to each triangle of another mesh, and how far apart are the two (BVH_QUERY_CLOSEST) — or is any tree triangle within the
+ * radius of it (BVH_QUERY_ANY)?  One bvh_tri_hit per query triangle: d_hits[i] answers triangle i of `queries`.  Clearance and tolerance checks between parts,
+ * contact generation with a margin (bodies that do not touch yet have an empty bvh_intersect_tris set), penetration-free stepping, mesh-to-mesh distance for
+ * registration.  bvh_closest_point on the other mesh's vertices misses every edge-edge and face-vertex minimum; this query does not.
+ * tree / tris: exactly as bvh_closest_point — any bvh_result in either layout (a build's, a refit's, an optimised or a caller-filled one on the ctx's device),
+ * triangles in any bvh_tri_format (NULL: tree->d_tris is read as Triangle[n_leaves]); nothing in the tree is written.  queries: as bvh_intersect_tris's with
+ * BVH_TRIS_QUERY — the other mesh's n_queries triangles, device pointers, any bvh_tri_format, independent of tris' (morton_bits is ignored).
+ * radius: ONE bound for the whole call; r2 = radius * radius in f32; +inf is no bound; a NaN or negative radius makes every query miss.
+ * The candidate of a pair: X = the query triangle, Y = the tree triangle, vertices v1, v2, v3.  Everything is f32 without contraction except the crossing
+ * test; every dot product is (x*x' + y*y') + z*z'; divisions are correctly rounded.  dist2(X, Y) and feature, in this order:
+ *   0. NaN.  If one of Y's nine coordinates is a NaN, dist2 = NaN and feature = 0: never accepted.  (A query triangle with a NaN coordinate misses, below.)
+ *   1. Crossing (feature 15).  If the stage-E boxes of X and Y overlap (bvh_overlap's box_overlap on bvh_stage_extents_ex's expression of either triangle,
+ *      clamps included) and proper(X) && proper(Y) && crosses(X, Y) — bvh_intersect_tris's predicate word for word, IEEE f64 on the f32 coordinates — then
+ *      dist2 = 0.0f and feature = 15.  Two triangles that cross share a point, which lies between the f32 minimum and maximum of either triangle's coordinates
+ *      on every axis: their stage-E boxes overlap exactly, so skipping the determinants where the boxes are disjoint changes no answer.
+ *   2. Vertices of X against Y (features 0, 1, 2): term k = tri_closest(Y.v1, Y.v2, Y.v3, X.v(k+1)), bvh_closest_point's formula word for word (its dist2).
+ *   3. Vertices of Y against X (features 3, 4, 5): term 3 + k = tri_closest(X.v1, X.v2, X.v3, Y.v(k+1)).
+ *   4. Edge i of X against edge j of Y (feature 6 + 3*i + j, i, j in 0..2), edges taken as (v1,v2), (v2,v3), (v3,v1): Ericson's ClosestPtSegmentSegment
+ *      (Real-Time Collision Detection, 5.1.9) for the segments (p1, q1) of X and (p2, q2) of Y, operation for operation:
+ *        d1 = q1 - p1;  d2 = q2 - p2;  r = p1 - p2;  a = dot(d1, d1);  e = dot(d2, d2);  f = dot(d2, r);   clamp(x) = x < 0 ? 0 : (x > 1 ? 1 : x)
+ *        if (a <= 0 && e <= 0)  s = 0, t = 0;
+ *        else if (a <= 0)       s = 0, t = clamp(f / e);
+ *        else { c = dot(d1, r);
+ *          if (e <= 0)          t = 0, s = clamp((-c) / a);
+ *          else { b = dot(d1, d2);  denom = a*e - b*b;
+ *                 s = denom != 0 ? clamp((b*f - c*e) / denom) : 0;
+ *                 t = (b*s + f) / e;
+ *                 if (t < 0)      t = 0, s = clamp((-c) / a);
+ *                 else if (t > 1) t = 1, s = clamp((b - c) / a); } }
+ *        w_k = (p1_k + d1_k*s) - (p2_k + d2_k*t);   term = (w.x*w.x + w.y*w.y) + w.z*w.z
+ *      (the book's EPSILON tests as exact tests against 0; a NaN passes through clamp).
+ *   Without a crossing, dist2 = the smallest of the 15 terms and feature = the LOWEST index that attains it: the minimum starts at +inf with feature 0 and a
+ *   term replaces it only when it is strictly smaller, in index order, so a NaN term never wins (if no term is below +inf, dist2 = +inf, feature 0).
+ * The 15 terms cover every closest pair of two disjoint triangles (the minimum is attained at a vertex of one, or between two edges); where two edges are nearly
+ * parallel and the segment formula's denom is weak, the end points' vertex terms hold the minimum.  Touching and coplanar overlap give a zero (or
+ * rounding-sized) vertex or edge term; only a proper crossing, whose 15 terms can all be positive, needs step 1.  `feature` lets a caller recompute the witness
+ * points with one evaluation of the stated term; the points themselves are not returned.
+ * Acceptance and answer: bvh_closest_point's, word for word.  A candidate is accepted iff dist2 <= r2.  BVH_QUERY_CLOSEST: the accepted candidate with the
+ * smallest (dist2, prim_idx), compared lexicographically — independent of the builder, the layout, the formats and the traversal order.  BVH_QUERY_ANY: some
+ * accepted candidate (the walk stops at the first); its record is that candidate's full dist2(X, Y) and feature.  A hit is written as {dist2, prim_idx, feature,
+ * 0}; a miss as {r2, BVH_INVALID, 0, 0}.  A query triangle with a NaN coordinate misses.  Degenerate query or tree triangles (points, segments) are ordinary
+ * candidates of steps 2-4; they cross nothing.
+ * Box tests are conservative: every node box grows on every axis by 2^-16 times its largest |coordinate|, the query triangle's stage-E box once
+ * the same way; the per-axis gap is fmaxf(fmaxf(lo_b - hi_q, lo_q - hi_b), 0) (a NaN plane is dropped), lb = (gx*gx + gy*gy) + gz*gz, and a subtree is kept
+ * iff lb * (1 - 2^-20) <= the best dist2 so far (r2 at the start).  A leaf pair whose own two stage-E boxes fail the same test is skipped.  Answers are exact
+ * on well-conditioned queries: the f64 squared distance between the two stage-E boxes of the true answer's pair, each grown by 2^-17 times its largest
+ * |coordinate|, is <= that answer's dist2.  On every query a reported hit is an accepted candidate of its prim with exactly its dist2 and feature, and a closest
+ * answer is never below the true best.
+ * Errors (nothing is written or enqueued, BVH_E_INVALID_ARG): bvh_closest_point's (NULL ctx / tree / d_hits, n_leaves < 2, layout not 0 or 1, NULL d_nodes,
+ * layout 1 with NULL d_leaves, root not an internal node, no triangles or a tris format error, query not 0 or 1, n_leaves larger than the ctx's capacity), NULL
+ * queries or a format error in it, n_queries >= 2^30, d_hits overlapping any node, leaf, triangle, vertex or index array of the call, the queries' included.
+ * n_queries == 0: 0, nothing is touched.
+ * Asynchronous on the ctx's stream, no read-back.  There is no depth limit: queries whose short stack would overflow are finished by a stackless pass through
+ * bvh_refit's parent plan, cached for the ctx's own tree and made per call for caller-owned arrays.  bvh_ctx_kernel_times reports k_closest_tris,
+ * k_closest_tris_deep and, when the plan is made, k_refit_plan. */
+int  bvh_closest_tris(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
+                      const bvh_build_input* queries /* the other mesh, device; any bvh_tri_format, independent of tris' */, uint32_t n_queries,
+                      float radius, bvh_tri_hit* d_hits /* [n_queries], device */, int query /* bvh_query_kind */);
+
 /* ---- early split clipping (Utility::doEarlySplitClipping, src/Utility.cpp:456-538: the PrimRef[] front end of the reference's LBVH builders) -------------
  * Large triangles become several REFERENCES {box, triangle index}: a box whose surface area exceeds sa_max is halved at its centre on its longest axis until
  * every piece is small enough, and the tree is then built over the pieces (bvh_build_boxes), so a wall that spans the scene no longer owns a scene-sized leaf.
