@@ -11,6 +11,7 @@
  *   bvh_tri_hit 16 B (bvh_closest_tris's output: the nearest tree triangle to a query triangle); no counterpart
  *   bvh_instance_knn_hit 16 B (one entry of bvh_scene_knn's lists and one record of bvh_scene_radius_search's slices: bvh_knn_hit with the instance, padded to one
  *     16-byte store); no counterpart
+ *   bvh_instance_tri_hit 16 B (bvh_scene_closest_tris's output: bvh_tri_hit with the instance in its last word); no counterpart
  *   bvh_instance_prim 8 B (one record of bvh_scene_overlap's, bvh_scene_intersect_tris's and bvh_scene_collide's slices: a primitive of an instance); no counterpart
  * Usable from C, C++ and HIP device code. */
 #ifndef BVH_TYPES_H
@@ -59,6 +60,9 @@ typedef struct { bvh_float3 point; float dist2; float u, v; uint32_t prim_idx, i
 /* one entry of a scene's k-nearest list (bvh_scene_knn) and one record of bvh_scene_radius_search's slices: the squared WORLD distance of instance
  * instance_idx's triangle prim_idx; reserved = 0 (an unused slot of a k-nearest list: {radius*radius, BVH_INVALID, BVH_INVALID, 0}; a slice has no unused slots) */
 typedef struct { float dist2; uint32_t prim_idx, instance_idx, reserved; } bvh_instance_knn_hit;
+/* bvh_scene_closest_tris's answer to one query triangle: dist2 = the squared WORLD distance to triangle prim_idx of instance instance_idx, feature as in
+ * bvh_tri_hit; a miss: {radius*radius, BVH_INVALID, 0, BVH_INVALID} */
+typedef struct { float dist2; uint32_t prim_idx; uint32_t feature; uint32_t instance_idx; } bvh_instance_tri_hit;
 /* one record of bvh_scene_overlap's, bvh_scene_intersect_tris's and bvh_scene_collide's slices: triangle prim_idx of instance instance_idx (a slice has no unused slots) */
 typedef struct { uint32_t prim_idx, instance_idx; } bvh_instance_prim;
 
@@ -79,6 +83,7 @@ static_assert(sizeof(bvh_instance) == 64, "bvh_instance is 64 bytes");
 static_assert(sizeof(bvh_instance_hit) == 32, "bvh_instance_hit is 32 bytes");
 static_assert(sizeof(bvh_instance_point_hit) == 32, "bvh_instance_point_hit is 32 bytes");
 static_assert(sizeof(bvh_instance_knn_hit) == 16, "bvh_instance_knn_hit is 16 bytes");
+static_assert(sizeof(bvh_instance_tri_hit) == 16, "bvh_instance_tri_hit is 16 bytes");
 static_assert(sizeof(bvh_instance_prim) == 8, "bvh_instance_prim is 8 bytes");
 #endif
 

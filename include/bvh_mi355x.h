@@ -1038,6 +1038,53 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  *     (row_capacity + 1 words) and d_prims (capacity records, clamped to 2^32 - 1) overlapping.
  *   bvh_ctx_kernel_times reports k_scene_collide_rows, k_scene_collide_count, k_scene_collide_fill, k_scene_collide_deep (after each pass) and
  *     k_overlap_scan.
+ * Mesh-to-scene distance: bvh_scene_closest_tris is bvh_closest_tris on a scene — which triangle of which active instance is nearest to each query triangle,
+ * and how far apart are the two (BVH_QUERY_CLOSEST), or is any within the radius (BVH_QUERY_ANY)?  Clearance of one body against the rest of an assembly,
+ * contact generation with a margin (bodies that do not touch yet have an empty bvh_scene_intersect_tris / bvh_scene_collide set), penetration-free stepping,
+ * tool-to-fixture distance, without flattening the scene and after bvh_scene_update alone.  One bvh_instance_tri_hit per query triangle.  The contract is the
+ * union of bvh_closest_tris's and bvh_scene_closest_point's; nothing in it is new arithmetic (tests/test_scene_closest_tris.py restates it in numpy).
+ *   tree-side triangle (k, j): the WORLD TRIANGLE of primitive j of instance k's BLAS, bvh_scene_closest_point's: with m_rc = object_to_world[4r + c],
+ *     V.r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3 for each of the three vertices, in f32 without contraction, in exactly this order.  Inactive instances never
+ *     answer.
+ *   query triangle i: bvh_scene_intersect_tris's, word for word.  BVH_SCENE_TRIS_QUERY — triangle i of `queries`, n_queries triangles already in world space,
+ *     device pointers, any bvh_tri_format (morton_bits is ignored); query_instance must be 0.  BVH_SCENE_TRIS_INSTANCE — `queries` must be NULL and query i is
+ *     the world triangle (query_instance, i); the instance is looked up ON THE DEVICE (no read-back; it follows a bvh_scene_update from device memory); a row at
+ *     or beyond that BLAS's n_leaves misses, every row of an inactive query instance misses; the walk skips instance query_instance BY INDEX, a second
+ *     instance of the same BLAS is another instance and answers.  As there, this mode reads triangle i of the BLAS's triangle array for every i < n_leaves and
+ *     is NOT usable on a BLAS over bvh_split_refs references relabelled by bvh_remap_leaves, which the call cannot check.
+ *   candidate of (i; k, j): bvh_closest_tris's dist2(X, Y) and feature with X = query triangle i and Y = the world triangle (k, j), all five steps word for
+ *     word: the NaN rule on Y; a proper crossing (feature 15, dist2 0) only where the two WORLD stage-E boxes overlap; the three vertex terms of X against Y;
+ *     the three of Y against X; the nine edge terms; the lowest index that attains the minimum wins.  The value does not depend on how the scene is walked.
+ *   acceptance and answer: r2 = radius * radius in f32, ONE bound for the whole call (+inf: no bound).  A candidate is accepted iff dist2 <= r2.  A NaN or
+ *     negative radius makes every query miss; a query triangle with a NaN coordinate misses.  BVH_QUERY_CLOSEST: the accepted candidate with the smallest
+ *     (dist2, instance_idx, prim_idx), compared lexicographically — independent of the top-level builder, the BLAS builders, the layouts, the formats and the
+ *     traversal order.  BVH_QUERY_ANY: some accepted candidate (the walk stops at the first); its record is that candidate's full dist2 and feature.
+ *     Hit = {dist2, prim_idx, feature, instance_idx}; miss = {r2, BVH_INVALID, 0, BVH_INVALID}.
+ *   box tests.  Top level: bvh_closest_tris's box_box_dist_pass on the instances' world boxes (each grown by 2^-16 * its largest |coordinate|) against the
+ *     query's world stage-E box grown once the same way; with n_instances == 1 the one world box is tested, then the instance entered.  Inside instance k: the
+ *     three query vertices x'_i = W_k x_i in the order of o' above; e = the largest over the three vertices of bvh_scene_closest_point's slack
+ *     2^-20 max_r(((|w_r0||x| + |w_r1||y|) + |w_r2||z|) + |w_r3|); the object query box is the componentwise min / max of the x'_i, grown on every axis by
+ *     2^-16 * (its largest |coordinate|) + e; a node box grows by 2^-16 * (its largest |coordinate|); the per-axis gap is
+ *     fmaxf(fmaxf(lo_b - hi_q, lo_q - hi_b), 0) (a NaN plane is dropped), lb' = (gx*gx + gy*gy) + gz*gz, and the subtree is culled iff
+ *     s2_k * lb' * (1 - 2^-20) > best (a NaN product never culls), s2_k being bvh_scene_closest_point's scale bound and best the world dist2 so far (r2 at the
+ *     start), carried across instances.  A leaf pair whose two WORLD stage-E boxes fail bvh_closest_tris's rule against best is skipped before any term is
+ *     computed.  (W_k is affine, so W_k x lies in the box of the W_k x_i for every point x of the query triangle, and
+ *     |M y - x|^2 >= s2 |y - W x|^2.)
+ *   well-conditioned (answers exact): for the true answer (k, j), (1) with x*_i = W_k x_i in f64 from the stored f32 entries, s2_k times the f64 squared gap
+ *     between the box of the x*_i grown by 2^-17 * (its largest |coordinate|) + e / 2 and triangle j's object box grown by 2^-17 * (its largest |coordinate|) is
+ *     <= the answer's dist2, and (2) the f64 squared gap between the query's world stage-E box and instance k's world box, each grown by 2^-17 * (its largest
+ *     |coordinate|), is <= that dist2.  On every query a reported hit is an accepted candidate of its (instance, prim) with bit-equal dist2 and feature, and a
+ *     closest answer is never lexicographically below the true one.
+ *   relation to the other queries: with one identity instance the hit records are bvh_closest_tris's on the BLAS byte for byte (its reserved 0 is instance 0),
+ *     misses equal but for the last word.  A row whose closest answer has feature 15 is a non-empty row of bvh_scene_intersect_tris; a non-empty row answers
+ *     dist2 = 0, with feature 15 unless a candidate that touches the query at exactly 0 by a vertex or edge term has the lower (instance_idx, prim_idx).
+ *   errors enqueue and write nothing (BVH_E_INVALID_ARG): a NULL or unbuilt scene; NULL d_hits; query not 0 or 1; mode not 0 or 1; NULL queries with
+ *     BVH_SCENE_TRIS_QUERY; queries given with BVH_SCENE_TRIS_INSTANCE; query_instance >= n_instances with BVH_SCENE_TRIS_INSTANCE, query_instance != 0 with
+ *     BVH_SCENE_TRIS_QUERY; n_queries >= 2^30; a format error in queries (as for bvh_scene_intersect_tris); d_hits overlapping the query mesh's triangle,
+ *     vertex or index array.  n_queries == 0: returns 0 and touches nothing.  BLAS ordering as for bvh_scene_intersect.
+ *   asynchronous on the ctx's stream, no read-back, no depth limit at either level (queries whose short stack would overflow are finished by a stackless pass
+ *     through the top-level plan and the BLAS plans, with the same boxes and candidates).  bvh_ctx_kernel_times reports k_scene_closest_tris and
+ *     k_scene_closest_tris_deep.
  * Winding numbers: bvh_scene_winding_number is bvh_winding_number on a scene — inside / outside against an assembly of bodies, the sign for
  * bvh_scene_closest_point's distance, voxelisation and point-in-union over thousands of bvh_build_many bodies — without flattening the scene.  Two calls:
  * bvh_scene_winding_prepare after a build or an update, bvh_scene_winding_number per batch of points (tests/test_scene_winding.py restates both in numpy).
@@ -1120,6 +1167,9 @@ int  bvh_scene_collide(bvh_scene* scene, uint32_t flags /* BVH_SCENE_COLLIDE_SOR
                        uint32_t* d_row_first /* u32[n_instances + 1], device */, uint32_t row_capacity,
                        uint32_t* d_offsets /* u32[row_capacity + 1], device */, bvh_instance_prim* d_prims /* [capacity], device, or NULL: count only */,
                        uint64_t capacity, uint64_t* rows_out /* host, may be NULL */, uint64_t* total_out /* host, may be NULL */);
+int  bvh_scene_closest_tris(bvh_scene* scene, const bvh_build_input* queries /* world-space mesh, device, any bvh_tri_format; NULL with BVH_SCENE_TRIS_INSTANCE */,
+                            uint32_t n_queries, int mode /* bvh_scene_tris_mode */, uint32_t query_instance /* BVH_SCENE_TRIS_INSTANCE only, else 0 */,
+                            float radius, bvh_instance_tri_hit* d_hits /* [n_queries], device */, int query /* bvh_query_kind */);
 #define BVH_SCENE_WINDING_KEEP_BLAS 1u
 int  bvh_scene_winding_prepare(bvh_scene* scene, uint32_t flags /* 0 or BVH_SCENE_WINDING_KEEP_BLAS */);
 int  bvh_scene_winding_number(bvh_scene* scene, const bvh_point_query* d_points /* radius ignored */, uint32_t n_points, float beta,
