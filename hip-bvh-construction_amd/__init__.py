@@ -86,7 +86,7 @@ EXPORTS = [
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap", "bvh_scene_intersect_tris", "bvh_scene_collide", "bvh_scene_closest_tris",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
-    "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris", "bvh_closest_tris",
+    "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris", "bvh_closest_tris", "bvh_radius_tris",
     "bvh_scene_winding_prepare", "bvh_scene_winding_number", "bvh_scene_winding_moments", "bvh_scene_winding_instances",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
 ]
@@ -129,6 +129,7 @@ OVERLAP_BOXES, OVERLAP_SELF = 0, 1   # bvh_overlap_mode
 TRIS_QUERY, TRIS_SELF = 0, 1         # bvh_tris_mode (bvh_intersect_tris)
 HITS_SORTED = 1                      # BVH_HITS_SORTED (bvh_intersect_all's flag)
 RADIUS_SORTED = 1                    # BVH_RADIUS_SORTED (bvh_radius_search's and bvh_scene_radius_search's flag)
+RADIUS_TRIS_SORTED, RADIUS_TRIS_SELF, RADIUS_TRIS_SKIP_SHARED = 1, 2, 4   # BVH_RADIUS_TRIS_* (bvh_radius_tris's flags)
 SCENE_OVERLAP_SORTED = 1             # BVH_SCENE_OVERLAP_SORTED (bvh_scene_overlap's flag)
 SCENE_TRIS_QUERY, SCENE_TRIS_INSTANCE = 0, 1   # bvh_scene_tris_mode (bvh_scene_intersect_tris)
 SCENE_TRIS_SORTED = 1                # BVH_SCENE_TRIS_SORTED (bvh_scene_intersect_tris's flag)
@@ -261,6 +262,7 @@ def lib() -> C.CDLL:
         "bvh_closest_tris": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(BuildInput), u32, C.c_float, vp, i32], i32),
         "bvh_intersect_all": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_radius_search": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_radius_tris": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(BuildInput), u32, C.c_float, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_winding_prepare": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp], i32),
         "bvh_winding_number": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, vp, u32, C.c_float, vp], i32),
         "bvh_split_refs": ([vp, C.POINTER(BuildInput), u32, C.c_float, u32, vp, vp, vp, u64, C.POINTER(u64)], i32),
@@ -1272,6 +1274,47 @@ class _Builder:
                 hits.free()
             if own is not None:
                 own.free()
+    def radius_tris(self, other=None, radius=None, self_pairs: bool = False, skip_shared: bool = True, sorted: bool = True, count_only: bool = False,
+                    capacity: int | None = None, tri_format: int = TRI_PADDED64, vertices=None, indices=None, n_vertices: int = 0, n: int | None = None,
+                    tree_tris=None, tree_vertices=None, tree_indices=None, tree_n_vertices: int = 0, tree_tri_format: int = TRI_PADDED64):
+        """bvh_radius_tris on this builder's tree: EVERY tree triangle within ``radius`` (one bound for the call; None: +inf) of each triangle of another mesh.
+        ``other`` as intersect_tris takes it: a host TRIANGLE array, a host (m, 9) or (m, 3, 3) float array (uploaded as TRI_PACKED36), or a device buffer of
+        records in ``tri_format`` (DeviceBuffer / int address, with ``n``); ``vertices`` / ``indices`` / ``n_vertices`` / ``n`` name a device TRI_INDEXED mesh
+        instead.  ``self_pairs=True`` is BVH_RADIUS_TRIS_SELF: no other mesh, the tree's own triangles against each other, every unordered pair once (j > i),
+        and with ``skip_shared`` (BVH_RADIUS_TRIS_SKIP_SHARED; read only with self_pairs) without the pairs that share a vertex; refused on a build_split tree,
+        which has more leaves than triangles (pass the mesh as ``other`` there).  The tree's triangles as for intersect_tris (tree_*).  Returns host arrays
+        (offsets u32[m + 1], hits TRI_HIT[total]): query triangle i's partners are hits[offsets[i]:offsets[i + 1]], {dist2, prim, feature, 0} each, in
+        ascending (dist2, prim) order when ``sorted`` (BVH_RADIUS_TRIS_SORTED; quadratic in a slice's length), in no particular order otherwise; an empty
+        slice is "nothing within the radius".  ``count_only`` returns offsets alone (the partner counts in scanned form).  ``capacity`` None: a count-only
+        call first, then a call with the exact capacity; a given capacity that is too small is re-allocated with the total the call reported and the call
+        repeated."""
+        if self._ctx is None:
+            raise BvhError("radius_tris needs a built tree")
+        ctx = self._ctx
+        own = None
+        qin = None
+        flags = RADIUS_TRIS_SORTED if sorted else 0
+        if self_pairs:
+            if other is not None or vertices is not None or indices is not None:
+                raise BvhError("self_pairs=True takes no other mesh")
+            if self._split is not None:
+                # (BVH_RADIUS_TRIS_SELF reads triangle i for every i < n_leaves; a build_split tree has more leaves — references — than triangles)
+                raise BvhError("self_pairs=True is not available on a build_split tree: it has more leaves than triangles; pass the mesh as `other` instead")
+            n = self.result.n_leaves
+            flags |= RADIUS_TRIS_SELF | (RADIUS_TRIS_SKIP_SHARED if skip_shared else 0)
+        else:
+            other, tri_format, n, own = _as_mesh(ctx, other, tri_format, vertices, indices, n, "self_pairs=True")
+            if n == 0:                                    # no queries: the empty answer, without a call
+                if own is not None:
+                    own.free()
+                return _no_queries(count_only, TRI_HIT)
+            qin = _build_input(tri_format, other, vertices, indices, n_vertices)
+        tree_tris, tree_tri_format = self._own_tris(tree_tris, tree_vertices, tree_indices, tree_tri_format)
+        tin = _tri_input(tree_tris, tree_vertices, tree_indices, tree_n_vertices, tree_tri_format)
+        r = float("inf") if radius is None else float(radius)
+        res = C.byref(self.result)
+        return _count_fill(ctx, lambda off, out, cap, tot: lib().bvh_radius_tris(ctx.handle, res, _ref(tin), _ref(qin), n, r, flags, off, out, cap, tot), n,
+                           TRI_HIT, count_only, capacity, f"{ALGO_NAMES[self.ALGO]}::radius_tris", own)
     def distance_to(self, other, **mesh):
         """-> (distance, query index, prim index): the distance between this builder's mesh and ``other`` (as closest_tris takes it, with its keyword
         arguments) — sqrt of the smallest dist2 of one unbounded "closest" call, the query triangle that attains it (the lowest index on a tie) and its nearest

@@ -539,7 +539,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_scene_closest_tris(); warm_scene_collide(); warm_scene_winding(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_closest_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_scene_closest_tris(); warm_scene_collide(); warm_scene_winding(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_closest_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_radius_tris(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -1171,6 +1171,43 @@ int bvh_closest_tris(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* 
     return query_tail(c, tree, overflow_words(c), [&](hipStream_t s, u32* overflow) {
         launch_closest_tris(s, (int)tree->layout, query, tm, qm, n_queries, radius, tree->d_nodes, tree->d_leaves, tree->n_leaves, tree->root, d_hits, overflow,
                             c->parent);
+    });
+}
+
+// ---- every triangle within a radius, mesh to mesh (no counterpart in the reference) ---------------------------------------------------------------
+// bvh_intersect_tris's checks (its self-mode rules on the flag bits, its ranges with bvh_tri_hit records in place of words) and bvh_radius_search's tail;
+// every argument is checked before anything is enqueued, so an error writes nothing
+int bvh_radius_tris(bvh_ctx* c, const bvh_result* tree, const bvh_build_input* tris, const bvh_build_input* queries, uint32_t n_queries, float radius,
+                    uint32_t flags, uint32_t* d_offsets, bvh_tri_hit* d_hits, uint64_t capacity, uint64_t* total_out) {
+    if (!c || !tree || !d_offsets) return BVH_E_INVALID_ARG;
+    if (flags & ~(BVH_RADIUS_TRIS_SORTED | BVH_RADIUS_TRIS_SELF | BVH_RADIUS_TRIS_SKIP_SHARED)) return BVH_E_INVALID_ARG;
+    const bool self = (flags & BVH_RADIUS_TRIS_SELF) != 0u;
+    if ((flags & BVH_RADIUS_TRIS_SKIP_SHARED) && !self) return BVH_E_INVALID_ARG;
+    if (self != (queries == nullptr)) return BVH_E_INVALID_ARG;                          // the other mesh, or none in self mode
+    if (!tree_valid(tree)) return BVH_E_INVALID_ARG;
+    const uint32_t n = tree->n_leaves;
+    if (self && n_queries != n) return BVH_E_INVALID_ARG;
+    if (n_queries >= (1u << 30)) return BVH_E_INVALID_ARG;
+    bvh_build_input in;
+    if (resolve_tris(tree, tris, &in)) return BVH_E_INVALID_ARG;
+    bvh_build_input qin = in;                                 // (self mode: the tree's own triangles)
+    if (queries) { if (stage_extents_valid(queries)) return BVH_E_INVALID_ARG; qin = *queries; }
+    if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
+    {   // the output arrays against each other and against everything the call reads
+        Range rs[8] = { Range(d_offsets, ((uint64_t)n_queries + 1u) * sizeof(u32)), fill_range(d_hits, capacity, sizeof(bvh_tri_hit)) };
+        int k = 2 + tree_ranges(tree, rs + 2);
+        k += mesh_ranges(in, n, rs + k);
+        if (queries) k += mesh_ranges(qin, n_queries, rs + k);
+        if (!disjoint(rs, 2, k)) return BVH_E_INVALID_ARG;
+    }
+    const TrisMesh tm{ (int)in.tri_format, in.d_tris, in.d_vertices, in.d_indices, in.n_vertices };
+    const TrisMesh qm{ (int)qin.tri_format, qin.d_tris, qin.d_vertices, qin.d_indices, qin.n_vertices };
+    return count_fill_tail(c, tree, n_queries, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
+        launch_radius_tris_count(s, (int)tree->layout, flags, tm, qm, n_queries, radius, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, overflow, c->parent,
+                                 c->overlap_sums, total);
+        if (d_hits)
+            launch_radius_tris_fill(s, (int)tree->layout, flags, tm, qm, n_queries, radius, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, d_hits, capacity,
+                                    total, overflow + 1, c->parent);
     });
 }
 

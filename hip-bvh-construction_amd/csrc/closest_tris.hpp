@@ -1,4 +1,5 @@
-// closest_tris.hpp — what the two mesh-to-mesh distance files share (closest_tris.hip: bvh_closest_tris; scene_closest_tris.hip: bvh_scene_closest_tris): the
+// closest_tris.hpp — what the mesh-to-mesh distance files share (closest_tris.hip: bvh_closest_tris; scene_closest_tris.hip: bvh_scene_closest_tris;
+// radius_tris.hip: bvh_radius_tris, which takes tt_dist2 and tris_query_load and keeps records of its own): the
 // exact candidate of a triangle pair (tt_dist2: the header's dist2(X, Y) and feature, restated in numpy by tests/test_closest_tris.py), the flat query's record
 // and the load of one query triangle.  The candidate is a value of the two triangles alone, so the scene form gets it by passing the WORLD triangle as Y.
 // Every file that includes this is built with -ffp-contract=off and without the SLP vectoriser (Makefile): the formulas are stated operation for operation.

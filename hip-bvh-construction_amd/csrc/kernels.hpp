@@ -233,6 +233,19 @@ void launch_tris_fill(hipStream_t s, int layout, int mode, const TrisMesh& tree_
 void launch_closest_tris(hipStream_t s, int layout, int query, const TrisMesh& tree_tris, const TrisMesh& queries, uint32_t n_queries, float radius,
                          const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root, void* d_hits, uint32_t* d_overflow, const uint32_t* d_parent);
 
+// ---- every triangle within a radius, mesh to mesh (radius_tris.hip): bvh_radius_tris's kernels.  tree_tris / queries as launch_tris_count's (self mode: the
+// same mesh twice); flags: the call's BVH_RADIUS_TRIS_* bits; radius: the call's one bound.  launch_radius_tris_count: k_radius_tris_walk (short stack;
+// d_offsets[i] = query triangle i's number of accepted candidates) + k_radius_tris_deep (stackless, returns at once while *d_overflow == 0) +
+// launch_overlap_scan.  launch_radius_tris_fill: the same two kernels' fill forms, which return at once unless *d_total <= capacity and *d_total < 2^32; query
+// i's bvh_tri_hit records go to d_hits[d_offsets[i] ..], in ascending (dist2, prim) order with BVH_RADIUS_TRIS_SORTED.  Each pass has an overflow word of its
+// own, zeroed before the launches
+void launch_radius_tris_count(hipStream_t s, int layout, uint32_t flags, const TrisMesh& tree_tris, const TrisMesh& queries, uint32_t n_queries, float radius,
+                              const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root, uint32_t* d_offsets, uint32_t* d_overflow,
+                              const uint32_t* d_parent, uint64_t* d_sums, uint64_t* d_total);
+void launch_radius_tris_fill(hipStream_t s, int layout, uint32_t flags, const TrisMesh& tree_tris, const TrisMesh& queries, uint32_t n_queries, float radius,
+                             const void* d_nodes, const void* d_leaves, uint32_t n, uint32_t root, uint32_t* d_offsets, void* d_hits, uint64_t capacity,
+                             const uint64_t* d_total, uint32_t* d_overflow, const uint32_t* d_parent);
+
 // ---- all-hits ray queries (multihit.hip): bvh_intersect_all's kernels, tree / triangle / ray arguments as launch_intersect's.  launch_hits_count: k_hits_count
 // (short stack; d_offsets[i] = ray i's number of accepted hits) + k_hits_deep (stackless, returns at once while *d_overflow == 0) + launch_overlap_scan.
 // launch_hits_fill: k_hits_fill + k_hits_deep, which return at once unless *d_total <= capacity and *d_total < 2^32; ray i's bvh_hit records go to
@@ -394,6 +407,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_tris(); void warm_scene_closest_tris(); void warm_scene_collide(); void warm_scene_winding(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_closest_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_split(); void warm_many(); void warm_many_ploc();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_tris(); void warm_scene_closest_tris(); void warm_scene_collide(); void warm_scene_winding(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_closest_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_radius_tris(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

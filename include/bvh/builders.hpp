@@ -221,6 +221,19 @@ public:
               "closestTris");
     }
 
+    // beyond the reference (bvh_radius_tris): EVERY triangle of this tree within `radius` of each of the n triangles of `queries`, as offsets +
+    // {dist2, prim, feature, 0} records (ascending (dist2, prim) per query with BVH_RADIUS_TRIS_SORTED in flags); against the same tree and triangles as
+    // intersect.  BVH_RADIUS_TRIS_SELF: queries nullptr, n = the tree's triangle count, every pair of the tree's own mesh once (j > i), with
+    // BVH_RADIUS_TRIS_SKIP_SHARED without the pairs that share a vertex.  d_hits NULL: count only.  total given: the call waits for the total and stores it;
+    // nullptr: asynchronous, the fill decides on the device whether the capacity suffices
+    void radiusTris(Context& context, const bvh_build_input* queries, u32 n, float radius, u32 flags, u32* d_offsets, bvh_tri_hit* d_hits, u64 capacity,
+                    u64* total = nullptr) {
+        uint64_t t = 0;
+        check(bvh_radius_tris(context.handle(), &m_result, m_triFormat == BVH_TRI_PADDED64 ? nullptr : &m_input, queries, n, radius, flags, d_offsets, d_hits,
+                              capacity, total ? &t : nullptr), "radiusTris");
+        if (total) *total = t;
+    }
+
     // beyond the reference (bvh_winding_prepare / bvh_winding_number): the generalized winding number of each point (1 inside a closed, outward-oriented mesh,
     // 0 outside), against the same tree and triangles as intersect.  d_moments: caller-owned bvh_winding_moment[n_leaves - 1], 16-byte aligned; prepare again
     // after a refit, an optimise or a rebuild.  The sign of a distance field: closestPoint's distance, negated where w > 0.5

@@ -668,6 +668,69 @@ int  bvh_closest_tris(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_inpu
                       const bvh_build_input* queries /* the other mesh, device; any bvh_tri_format, independent of tris' */, uint32_t n_queries,
                       float radius, bvh_tri_hit* d_hits /* [n_queries], device */, int query /* bvh_query_kind */);
 
+/* ---- every triangle within a radius, mesh to mesh (no counterpart in the reference) ------------------------------------------------------
+ * Which triangles of the tree lie within the radius of each triangle of another mesh, ALL of them, how far away, and between which two features — or, with
+ * BVH_RADIUS_TRIS_SELF, which pairs of the tree's own mesh?  The third proximity answer of the triangle queries, beside bvh_intersect_tris (every crossing
+ * pair) and bvh_closest_tris (the one nearest): cloth and shell contact with a thickness, barrier and penalty methods that need every vertex-face and
+ * edge-edge pair closer than a distance, clearance reports that list every violating pair, proximity constraints between parts.  One walk instead of
+ * bvh_overlap with inflated boxes and an exact filter on the host, which sends the whole box-pair list through memory.
+ * tree / tris / queries: exactly as bvh_closest_tris — any bvh_result in either layout (a build's, a refit's, an optimised or a caller-filled one on the ctx's
+ * device), triangles in any bvh_tri_format (NULL: tree->d_tris is read as Triangle[n_leaves]); nothing in the tree is written.  queries: the other mesh's
+ * n_queries triangles, device pointers, any bvh_tri_format, independent of tris' (morton_bits is ignored); NULL with BVH_RADIUS_TRIS_SELF.
+ * Candidate: dist2(X, Y) and feature are bvh_closest_tris's, steps 0-4 word for word, X = the query triangle, Y = the tree triangle (one device function
+ * serves both calls).
+ * Acceptance: dist2 <= r2, r2 = radius * radius in f32; radius is ONE bound for the whole call.  An infinite radius accepts every pair whose dist2 is not NaN
+ * (a tree triangle with a NaN vertex is never accepted).  A NaN or negative radius makes every query dead, and so does a NaN coordinate in the query triangle:
+ * a dead query accepts nothing.  radius 0 (or -0) accepts the pairs at dist2 == 0, proper crossings (feature 15) among them.
+ * Answer: query triangle i's set is ALL its accepted candidates, as {dist2, prim_idx, feature, 0} records (bvh_tri_hit) in compressed-row form, as
+ * bvh_radius_search's: d_hits[d_offsets[i] .. d_offsets[i+1]) is query i's slice, d_offsets[0] = 0, d_offsets[n_queries] = the total.  Each primitive appears
+ * at most once per slice.  There is no padding and there are no miss records: an empty slice is "nothing within r".  With d_hits == NULL the call only counts:
+ * d_offsets is then the queries' partner counts in scanned form.
+ * Order inside a slice: without BVH_RADIUS_TRIS_SORTED unspecified, but the same call on the same arrays gives the same bytes.  With BVH_RADIUS_TRIS_SORTED
+ * each slice is in ascending (dist2, prim_idx) order, compared lexicographically (an accepted dist2 is never NaN or negative); the whole d_hits array then does
+ * not depend on the builder, the layout, the scheduler, the triangle formats or the traversal order, and the first record of a non-empty slice is
+ * bvh_closest_tris(BVH_QUERY_CLOSEST)'s record for the same radius, bit for bit.  The sorted fill inserts each record into its slice as it is found, which is
+ * quadratic in the slice's length: very long sorted slices (thousands of partners per query) are the caller's to avoid, or to fill unsorted and sort themselves.
+ * Box tests are bvh_closest_tris's conservative test (every node box grows on every axis by 2^-16 times its largest |coordinate|, the query
+ * triangle's stage-E box once the same way, lb = the f32 sum of the squared per-axis gaps, the subtree is kept iff lb * (1 - 2^-20) <= the bound) against r2
+ * for the whole walk: the bound never shrinks.  A leaf pair whose own two stage-E boxes fail the same test is skipped before any term is computed.  A query is
+ * well-conditioned when every accepted pair satisfies bvh_closest_tris's condition: the f64 squared distance between the pair's two stage-E boxes, each grown by
+ * 2^-17 times its largest |coordinate|, is <= the pair's dist2.  On such queries no ancestor of an accepted triangle is culled and the set is exact (DESIGN.md
+ * 8z).  On EVERY query each reported record is an accepted candidate of its primitive with a bit-equal dist2 and feature, and the slice is a subset of the true
+ * set.
+ * BVH_RADIUS_TRIS_SELF: the queries are the tree's own triangles (tris), queries must be NULL, n_queries must equal n_leaves, and only j > i is reported: each
+ * unordered pair once, as j in i's slice, and no triangle with itself.  The call reads triangle i of tris for EVERY i < n_leaves, so tris must hold n_leaves
+ * triangles: as BVH_TRIS_SELF, it is NOT usable on a tree with more leaves than triangles (a tree over bvh_split_refs references relabelled by
+ * bvh_remap_leaves); pass the mesh itself as queries there (the Python binding refuses self_pairs on a build_split tree).  On such a tree a pair can appear
+ * once per reference reached; this is not deduplicated.
+ * BVH_RADIUS_TRIS_SKIP_SHARED (only together with SELF): on one mesh every topological neighbour is at distance 0, which is not contact.  A pair is skipped
+ * when any vertex of X equals any vertex of Y on all three coordinates under IEEE == — so -0 equals +0 and a NaN equals nothing.  No adjacency input and no
+ * index comparison: it works in all three triangle formats.  It is evaluated at the leaf before the terms, identically in count and fill.
+ * Passes: the call always counts, then scans the counts into d_offsets, and keeps the 64-bit total in a device word.  It fills d_hits iff d_hits != NULL,
+ * total <= capacity and total < 2^32; that decision is made ON THE DEVICE (the fill launch reads the total word and returns at once), so the call stays
+ * asynchronous on the ctx's stream.  If the fill is skipped d_hits is not touched and d_offsets is still complete.  With total_out != NULL the call blocks on
+ * an 8-byte read-back into pinned words and stores the total; a host that guessed too small a capacity re-allocates and calls again.  A total of 2^32 or more
+ * saturates d_offsets at 0xFFFFFFFF; if total_out was given the call then returns BVH_E_TOO_LARGE (with *total_out set).  d_hits is never written outside
+ * query i's slice, nor past the total.
+ * There is no depth limit: a query whose short stack would overflow, or whose walk exceeds the node count, is redone by a stackless pass through bvh_refit's
+ * parent plan, cached for the ctx's own tree as for bvh_intersect and made per call for caller-owned arrays.  Count and fill agree on every query's set
+ * whichever pass served it.
+ * Errors (nothing is written or enqueued, BVH_E_INVALID_ARG): bvh_closest_tris's without the query kind (NULL ctx / tree, n_leaves < 2, layout not 0 or 1,
+ * NULL d_nodes, layout 1 with NULL d_leaves, root not an internal node, no triangles or a tris format error, a format error in queries, n_leaves larger than the
+ * ctx's capacity: call bvh_ctx_reserve first); NULL d_offsets; a flag bit other than the three below; BVH_RADIUS_TRIS_SKIP_SHARED without BVH_RADIUS_TRIS_SELF;
+ * NULL queries without BVH_RADIUS_TRIS_SELF; queries given with BVH_RADIUS_TRIS_SELF; BVH_RADIUS_TRIS_SELF with n_queries != n_leaves; n_queries >= 2^30;
+ * d_offsets or d_hits (capacity records) overlapping each other or a node, leaf, triangle, vertex or index array of the call.
+ * n_queries == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.
+ * bvh_ctx_kernel_times reports k_radius_tris_walk (count and fill), k_radius_tris_deep (after each pass), k_overlap_scan (the scan is bvh_overlap's) and, when
+ * the plan is made, k_refit_plan. */
+#define BVH_RADIUS_TRIS_SORTED       1u
+#define BVH_RADIUS_TRIS_SELF         2u
+#define BVH_RADIUS_TRIS_SKIP_SHARED  4u   /* only together with BVH_RADIUS_TRIS_SELF */
+int  bvh_radius_tris(bvh_ctx* ctx, const bvh_result* tree, const bvh_build_input* tris /* NULL: tree->d_tris is Triangle[n_leaves] */,
+                     const bvh_build_input* queries /* the other mesh, device; any bvh_tri_format, independent of tris'; NULL with BVH_RADIUS_TRIS_SELF */,
+                     uint32_t n_queries, float radius, uint32_t flags /* BVH_RADIUS_TRIS_* */, uint32_t* d_offsets /* u32[n_queries + 1], device */,
+                     bvh_tri_hit* d_hits /* [capacity], device, or NULL: count only */, uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+
 /* ---- early split clipping (Utility::doEarlySplitClipping, src/Utility.cpp:456-538: the PrimRef[] front end of the reference's LBVH builders) -------------
  * Large triangles become several REFERENCES {box, triangle index}: a box whose surface area exceeds sa_max is halved at its centre on its longest axis until
  * every piece is small enough, and the tree is then built over the pieces (bvh_build_boxes), so a wall that spans the scene no longer owns a scene-sized leaf.
