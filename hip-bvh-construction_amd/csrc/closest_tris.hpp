@@ -77,7 +77,7 @@ __device__ __forceinline__ void tri_hit_store(bvh_tri_hit* hits, u32 i, const TB
 
 // one query triangle: its vertices, whether it is live (no NaN coordinate, radius >= 0; a NaN radius fails the comparison) and r2 = radius * radius either way
 __device__ __forceinline__ bool tris_query_load(int qfmt, const TriSrc& qsrc, u32 i, float radius, QF3& x1, QF3& x2, QF3& x3, float& r2) {
-    tt_query_fetch(qfmt, qsrc, i, x1, x2, x3);
+    tri_fetch_rt(qfmt, qsrc, i, x1, x2, x3);
     r2 = radius * radius;
     return tt_numbers(x1, x2, x3) && radius >= 0.0f;
 }

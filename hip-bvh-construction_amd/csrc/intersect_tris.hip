@@ -46,7 +46,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_tris_walk(TriSrc qsrc, int qfmt
     }
     u32* const stack = s_stack + tid_x();
     QF3 x1, x2, x3;
-    tt_query_fetch(qfmt, qsrc, i, x1, x2, x3);
+    tri_fetch_rt(qfmt, qsrc, i, x1, x2, x3);
     const Box q = tt_box(x1, x2, x3);
     bool deep = false;
     if (box_valid(q) && tt_proper(x1, x2, x3)) {                  // (an axis that is all NaN or all +inf keeps the reset planes: inverted, overlaps nothing; a
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_tris_deep(TriSrc qsrc, int qfmt
             sink.out = prims + base; sink.room = end - base;
         } else if (offsets[i] != QUERY_MARK) continue;
         QF3 x1, x2, x3;
-        tt_query_fetch(qfmt, qsrc, i, x1, x2, x3);
+        tri_fetch_rt(qfmt, qsrc, i, x1, x2, x3);
         const Box q = tt_box(x1, x2, x3);                         // (a marked query passed box_valid and tt_proper)
         u32 cur = root, last = INV;
         bool down = true;

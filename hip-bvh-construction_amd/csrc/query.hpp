@@ -57,9 +57,14 @@ __device__ __forceinline__ void tri_fetch(const TriSrc& s, u32 prim, QF3& a, QF3
     }
 }
 
+// how far every plane of box b moves out in a conservative test: QUERY_GROW times the box's largest |coordinate| (the one statement of it: DESIGN.md §8b, §8e, §8n)
+__device__ __forceinline__ float box_grow(const Box& b) {
+    return QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz)));
+}
+
 // conservative slab test of box b against [tmin, best]: true iff the box may hold an accepted hit; tn_out = the interval's (unwidened) entry for ordering
 __device__ __forceinline__ bool box_pass(const Box& b, const QRay& r, float best, float& tn_out) {
-    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz)));
+    const float g = box_grow(b);
     const float lx = b.lx - g, ly = b.ly - g, lz = b.lz - g, hx = b.hx + g, hy = b.hy + g, hz = b.hz + g;
     const float tnx = ((r.nx ? hx : lx) - r.o.x) * r.inv.x, tfx = ((r.nx ? lx : hx) - r.o.x) * r.inv.x;
     const float tny = ((r.ny ? hy : ly) - r.o.y) * r.inv.y, tfy = ((r.ny ? ly : hy) - r.o.y) * r.inv.y;
@@ -128,7 +133,7 @@ __device__ __forceinline__ float tri_closest(QF3 a, QF3 b, QF3 c, QF3 p, QF3& q,
 // conservative distance test of box b against best (a squared distance): true iff the box may hold an accepted candidate; lb_out = the
 // grown box's f32 squared distance, for ordering.  The box grows as in box_pass; fmaxf drops the NaN of a NaN or infinite plane (the axis then costs 0).
 __device__ __forceinline__ bool box_dist_pass(const Box& b, QF3 p, float best, float& lb_out) {
-    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz)));
+    const float g = box_grow(b);
     const float dx = fmaxf(fmaxf((b.lx - g) - p.x, p.x - (b.hx + g)), 0.0f);
     const float dy = fmaxf(fmaxf((b.ly - g) - p.y, p.y - (b.hy + g)), 0.0f);
     const float dz = fmaxf(fmaxf((b.lz - g) - p.z, p.z - (b.hz + g)), 0.0f);
@@ -139,7 +144,7 @@ __device__ __forceinline__ bool box_dist_pass(const Box& b, QF3 p, float best, f
 
 // a query box grown once for box_box_dist_pass: every plane moves out by QUERY_GROW * (the box's largest |coordinate|), as box_dist_pass grows a node box
 __device__ __forceinline__ Box box_grown(const Box& b) {
-    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz)));
+    const float g = box_grow(b);
     return { b.lx - g, b.ly - g, b.lz - g, b.hx + g, b.hy + g, b.hz + g };
 }
 
@@ -147,7 +152,7 @@ __device__ __forceinline__ Box box_grown(const Box& b) {
 // here.  The per-axis gap is the larger of the two one-sided gaps, or 0 where the intervals overlap; lb_out = the f32 sum of the squared gaps, for ordering.
 // fmaxf drops the NaN of a NaN or infinite plane (the axis then costs 0).  True iff the box may hold an accepted candidate
 __device__ __forceinline__ bool box_box_dist_pass(const Box& b, const Box& qg, float best, float& lb_out) {
-    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz)));
+    const float g = box_grow(b);
     const float dx = fmaxf(fmaxf((b.lx - g) - qg.hx, qg.lx - (b.hx + g)), 0.0f);
     const float dy = fmaxf(fmaxf((b.ly - g) - qg.hy, qg.ly - (b.hy + g)), 0.0f);
     const float dz = fmaxf(fmaxf((b.lz - g) - qg.hz, qg.lz - (b.hz + g)), 0.0f);
@@ -192,6 +197,12 @@ __device__ __forceinline__ QF3 xf_point(const float* m, float x, float y, float 
 __device__ __forceinline__ void rec_fetch_rt(int layout, const void* nodes, const void* leaves, u32 c, u32 ni, u32& w0, u32& w1, Box& b) {
     if (layout == 0) rec_fetch<0>(reinterpret_cast<const bvh2_node*>(nodes), nullptr, c, ni, w0, w1, b);
     else rec_fetch<1>(reinterpret_cast<const bvh2_node*>(nodes), reinterpret_cast<const bvh_primref*>(leaves), c, ni, w0, w1, b);
+}
+// tri_fetch with the format chosen at run time (uniform per mesh: over a launch for a query mesh, per BLAS in a scene)
+__device__ __forceinline__ void tri_fetch_rt(int fmt, const TriSrc& s, u32 prim, QF3& a, QF3& b, QF3& c) {
+    if (fmt == BVH_TRI_PADDED64) tri_fetch<BVH_TRI_PADDED64>(s, prim, a, b, c);
+    else if (fmt == BVH_TRI_PACKED36) tri_fetch<BVH_TRI_PACKED36>(s, prim, a, b, c);
+    else tri_fetch<BVH_TRI_INDEXED>(s, prim, a, b, c);
 }
 
 } // namespace bvh

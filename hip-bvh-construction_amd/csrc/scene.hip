@@ -1,12 +1,11 @@
 // scene.hip — bvh_scene on gfx950: instanced scenes, two levels (no counterpart in the reference).  A top-level tree (TLAS) over the instances' world boxes,
 // whose leaves are instances, and per instance a bottom-level tree (BLAS) traversed with the ray mapped into the instance's object space.  One ray per lane; the
 // BLAS's layout and triangle format are read from its 64-byte descriptor when the ray enters the instance and dispatched at run time (uniform per instance).
-// The hit test, box test and loads are query.hpp's, shared with k_intersect.  DESIGN.md §8d.
+// The hit test, box test and loads are query.hpp's, shared with k_intersect; the entry into an instance and the BLAS's triangle are scene_query.hpp's.  DESIGN.md §8d.
 // Compiled WITHOUT the SLP vectoriser (Makefile): with it, the record update of an equal-t replacement (a tie decided by the prim index) kept the losing
 // candidate's v while taking the winner's t / u / prim — the vectoriser packs the divisions of the hit test into <iu, it> / <iv, iw> pairs that reach the record
 // through separate phi chains.  Found by tests/test_gpu_scene.py (one identity instance against bvh_intersect, Sponza-like mesh: 682 of 4096 rays).
-#include "query.hpp"
-#include "kernels.hpp"
+#include "scene_query.hpp"
 
 namespace bvh {
 
@@ -49,10 +48,9 @@ __global__ __launch_bounds__(SCENE_INST_BLOCK) void k_instance_boxes(const bvh_i
     const u32 k = bid_x() * SCENE_INST_BLOCK + tid_x();
     if (k >= n_inst) return;
     const float4* q = reinterpret_cast<const float4*>(instances + k);
-    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
+    float m[12], w[12];
+    mat_rows({ q[0], q[1], q[2] }, m);
     const u32 bl = __float_as_uint(q[3].x);
-    const float m[12] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
-    float w[12];
     const bool ok = instance_inverse(m, w) && bl < n_blas;
     Box wb = box_empty();
     if (ok) {
@@ -70,31 +68,12 @@ __global__ __launch_bounds__(SCENE_INST_BLOCK) void k_instance_boxes(const bvh_i
     box_store(wbox + k, wb);
 }
 
-// the world ray w in instance k's object space (tmin / tmax kept); false: inactive instance
-__device__ __forceinline__ bool enter_instance(const SceneQuery& a, u32 k, const QRay& w, QRay& r, SceneBlas& B) {
-    const float4* q = reinterpret_cast<const float4*>(a.inst + k);
-    const u32 bl = __float_as_uint(q[3].x);
-    if (bl == INV) return false;
-    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
-    const float m[12] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
-    B = a.blas[bl];
-    r.o = xf_point(m, w.o.x, w.o.y, w.o.z);
-    r.d = { (m[0] * w.d.x + m[1] * w.d.y) + m[2] * w.d.z, (m[4] * w.d.x + m[5] * w.d.y) + m[6] * w.d.z, (m[8] * w.d.x + m[9] * w.d.y) + m[10] * w.d.z };
-    r.inv = { 1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z };
-    r.nx = __float_as_uint(r.d.x) >> 31; r.ny = __float_as_uint(r.d.y) >> 31; r.nz = __float_as_uint(r.d.z) >> 31;
-    r.tmin = w.tmin; r.tmax = w.tmax;
-    return true;
-}
-
 // leaf_test with the BLAS's format chosen at run time and the scene's order (t, instance, prim); true when an any-hit query is done
 template <int QUERY>
 __device__ __forceinline__ bool scene_leaf_test(const SceneBlas& B, u32 prim, u32 inst, const QRay& r, float& bt, float& bu, float& bv, u32& bp, u32& bi) {
     if (prim >= B.n) return false;
-    const TriSrc src{ B.tris, reinterpret_cast<const float*>(B.tris), reinterpret_cast<const u32*>(B.idx), B.nv };
     QF3 a, b, c;
-    if (B.fmt == BVH_TRI_PADDED64) tri_fetch<BVH_TRI_PADDED64>(src, prim, a, b, c);
-    else if (B.fmt == BVH_TRI_PACKED36) tri_fetch<BVH_TRI_PACKED36>(src, prim, a, b, c);
-    else tri_fetch<BVH_TRI_INDEXED>(src, prim, a, b, c);
+    blas_tri_fetch(B, prim, a, b, c);
     float it = 0.0f, iu = 0.0f, iv = 0.0f;                     // (defined on every path: the record below is taken whole or not at all)
     const bool hit = tri_hit(a, b, c, r, it, iu, iv) && r.tmin < it && it < r.tmax;
     const bool take = hit && (QUERY == BVH_QUERY_ANY || it < bt || (it == bt && (inst < bi || (inst == bi && prim < bp))));
@@ -137,7 +116,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_intersect(SceneQuery a) {
             if (entering) {
                 entering = false;
                 const u32 k = enter;
-                if (k < a.n_inst && enter_instance(a, k, w, r, B)) {
+                if (k < a.n_inst && enter_instance_ray(a, k, w, r, B)) {
                     in_blas = true; inst = k; ni = B.n - 1; total = 2 * B.n - 1; bsteps = 0;
                     const uint2 lr = *reinterpret_cast<const uint2*>(reinterpret_cast<const bvh2_node*>(B.nodes) + B.root); nl = lr.x; nr = lr.y;
                 } else pop = true;
@@ -193,7 +172,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_intersect(SceneQuery a) {
 template <int QUERY>
 __device__ bool scene_walk_blas(const SceneQuery& a, u32 k, const QRay& w, float& bt, float& bu, float& bv, u32& bp, u32& bi) {
     QRay r; SceneBlas B;
-    if (k >= a.n_inst || !enter_instance(a, k, w, r, B)) return false;
+    if (k >= a.n_inst || !enter_instance_ray(a, k, w, r, B)) return false;
     const u32 ni = B.n - 1, total = 2 * B.n - 1;
     const u64 bound = 3ull * total + 3ull;
     u32 cur = B.root, last = INV;

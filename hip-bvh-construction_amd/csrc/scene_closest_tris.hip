@@ -3,8 +3,8 @@
 // feature (tt_dist2, closest_tris.hpp) with Y the WORLD triangle — the BLAS's vertices mapped by the instance's forward matrix (st_world_tri, scene_map.hpp) —
 // so dist2 and feature are world-space values that do not depend on the walk.  The walk itself runs in object space, as scene_point.hip's: inside instance k the
 // three query vertices are mapped as x'_i = W_k x_i, and a node box is tested against
-//   the componentwise min/max box of the x'_i, grown on every axis by QUERY_GROW * (its largest |coordinate|) + e,  e = the largest of scene_point.hip's slack
-//   over the three vertices;   the node box grown by QUERY_GROW * (its largest |coordinate|);   culled iff s2 * lb' * (1 - 2^-20) > best,
+//   the componentwise min/max box of the x'_i, grown on every axis by QUERY_GROW * (its largest |coordinate|) + e,  e = the largest of the point queries' slack
+//   (scene_slack, scene_query.hpp) over the three vertices;   the node box grown by QUERY_GROW * (its largest |coordinate|);   culled iff s2 * lb' * (1 - 2^-20) > best,
 // with lb' the f32 sum of the squared per-axis gaps (box_box_dist_pass's), s2 the instance's scale bound and best the world dist2 so far, carried across
 // instances.  DESIGN.md §8y has the argument (§8n's for every point of the query triangle: W is affine, so W x lies in the box of the W x_i).  The top level is
 // box_box_dist_pass on the world boxes with the query's stage-E box grown once: the same test with s2 = 1, which is how the shared loop states it (1 * lb is
@@ -39,7 +39,7 @@ struct SCBox { Box q; float s2; };
 struct SCWalk { const void* nodes; const void* leaves; u32 n, layout, bl; };
 
 __device__ __forceinline__ bool scene_box_box_pass(const Box& b, const SCBox& c, float best, float& lb_out) {
-    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz)));
+    const float g = box_grow(b);
     const float dx = fmaxf(fmaxf((b.lx - g) - c.q.hx, c.q.lx - (b.hx + g)), 0.0f);
     const float dy = fmaxf(fmaxf((b.ly - g) - c.q.hy, c.q.ly - (b.hy + g)), 0.0f);
     const float dz = fmaxf(fmaxf((b.lz - g) - c.q.hz, c.q.lz - (b.hz + g)), 0.0f);
@@ -51,29 +51,20 @@ __device__ __forceinline__ bool scene_box_box_pass(const Box& b, const SCBox& c,
 // the query's world box for the top level: its stage-E box grown once
 __device__ __forceinline__ SCBox sc_world_box(QF3 x1, QF3 x2, QF3 x3) { return { box_grown(tt_box(x1, x2, x3)), 1.0f }; }
 
-// scene_point.hip's slack of one world vertex against the rows of W
-__device__ __forceinline__ float sc_slack(const float* m, QF3 w) {
-    const float ax = fabsf(w.x), ay = fabsf(w.y), az = fabsf(w.z);
-    const float r0 = ((fabsf(m[0]) * ax + fabsf(m[1]) * ay) + fabsf(m[2]) * az) + fabsf(m[3]);
-    const float r1 = ((fabsf(m[4]) * ax + fabsf(m[5]) * ay) + fabsf(m[6]) * az) + fabsf(m[7]);
-    const float r2 = ((fabsf(m[8]) * ax + fabsf(m[9]) * ay) + fabsf(m[10]) * az) + fabsf(m[11]);
-    return 0x1p-20f * fmaxf(fmaxf(r0, r1), r2);
-}
-
 // the world query triangle in instance k's object space: its grown box, the instance's scale bound and BLAS; false: inactive instance
 __device__ __forceinline__ bool enter_instance_tris(const SceneQuery& a, u32 k, QF3 x1, QF3 x2, QF3 x3, SCBox& c, SceneBlas& B, u32& bl_out) {
     const float4* q = reinterpret_cast<const float4*>(a.inst + k);
     const float4 q3 = q[3];
     const u32 bl = __float_as_uint(q3.x);
     if (bl == INV) return false;
-    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
-    const float m[12] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
+    float m[12];
+    mat_rows({ q[0], q[1], q[2] }, m);
     B = a.blas[bl]; bl_out = bl;
     const QF3 p1 = xf_point(m, x1.x, x1.y, x1.z), p2 = xf_point(m, x2.x, x2.y, x2.z), p3 = xf_point(m, x3.x, x3.y, x3.z);
-    const float e = fmaxf(fmaxf(sc_slack(m, x1), sc_slack(m, x2)), sc_slack(m, x3));
+    const float e = fmaxf(fmaxf(scene_slack(m, x1), scene_slack(m, x2)), scene_slack(m, x3));
     const Box o{ fminf(fminf(p1.x, p2.x), p3.x), fminf(fminf(p1.y, p2.y), p3.y), fminf(fminf(p1.z, p2.z), p3.z),
                  fmaxf(fmaxf(p1.x, p2.x), p3.x), fmaxf(fmaxf(p1.y, p2.y), p3.y), fmaxf(fmaxf(p1.z, p2.z), p3.z) };
-    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(o.lx), fabsf(o.hx)), fmaxf(fabsf(o.ly), fabsf(o.hy))), fmaxf(fabsf(o.lz), fabsf(o.hz))) + e;
+    const float g = box_grow(o) + e;
     c.q = { o.lx - g, o.ly - g, o.lz - g, o.hx + g, o.hy + g, o.hz + g };
     c.s2 = q3.y;
     return true;
@@ -85,10 +76,8 @@ __device__ __forceinline__ bool enter_instance_tris(const SceneQuery& a, u32 k, 
 template <int QUERY>
 __device__ __forceinline__ bool scene_leaf_tris(const SceneQuery& a, u32 bl, u32 prim, u32 inst, QF3 x1, QF3 x2, QF3 x3, bool xproper, SCBest& best) {
     const SceneBlas B = a.blas[bl];
-    const float4* mq = reinterpret_cast<const float4*>(reinterpret_cast<const bvh_instance*>(a.inst_in) + inst);
-    const SOMat M{ mq[0], mq[1], mq[2] };
     QF3 y1, y2, y3;
-    st_world_tri(B, M, prim, y1, y2, y3);
+    st_world_tri(B, inst_load_m(a, inst), prim, y1, y2, y3);
     const Box xb = tt_box(x1, x2, x3), xg = box_grown(xb), yb = tt_box(y1, y2, y3);
     float lb;
     if (!box_box_dist_pass(yb, xg, best.d2, lb)) return false;    // the pair's own world boxes are already too far apart for the current best
@@ -108,7 +97,7 @@ __device__ __forceinline__ void scene_tri_hit_store(void* hits, u32 i, const SCB
 template <int MODE>
 __device__ __forceinline__ bool sc_query_load(const SceneQuery& a, const SCQuery& t, u32 i, QF3& x1, QF3& x2, QF3& x3, float& r2) {
     r2 = t.radius * t.radius;
-    if (MODE == BVH_SCENE_TRIS_QUERY) tt_query_fetch(t.fmt, t.src, i, x1, x2, x3);
+    if (MODE == BVH_SCENE_TRIS_QUERY) tri_fetch_rt(t.fmt, t.src, i, x1, x2, x3);
     else {
         SOMat M; SceneBlas B;
         if (t.inst >= a.n_inst || !sov_enter_instance(a, t.inst, M, B) || i >= B.n) return false;

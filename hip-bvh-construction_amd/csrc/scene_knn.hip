@@ -1,7 +1,7 @@
 // scene_knn.hip — bvh_scene_knn on gfx950: the k nearest triangles of each query point within its radius, over all active instances of a scene (no counterpart
 // in the reference).  One query per lane.  It is scene_point.hip's walk with knn.hip's list: the candidate of (instance k, primitive j) is tri_closest on the
 // WORLD triangle (the BLAS's vertices mapped by the instance's forward matrix), the walk inside an instance runs in object space against the mapped point
-// p' = W_k p with the box grown by QUERY_GROW * (its largest |coordinate|) + e and culled iff s2 * lb' * (1 - 2^-20) > bound, and bound is the
+// p' = W_k p with the box grown by QUERY_GROW * (its largest |coordinate|) + e and culled iff s2 * lb' * (1 - 2^-20) > bound (scene_query.hpp), and bound is the
 // dist2 of the list's last entry once the list holds k entries (r2 before that), carried across instances and level changes.
 //   k_scene_knn      : one per-lane LDS short stack shared by both levels (k_scene_closest_point's structure and walk order: near child first by lower bound
 //                      at both levels, la <= lb goes left), leaf children whose box passes tested at once, the forward matrix re-loaded per leaf test.  With
@@ -16,16 +16,12 @@
 // k_scene_knn_deep keeps lane-per-query stores.
 // Built without the SLP vectoriser (Makefile), as scene_point.o and knn.o: the list update is the same tie-breaking pattern.
 #include <type_traits>
-#include "query.hpp"
-#include "kernels.hpp"
+#include "scene_query.hpp"
 
 namespace bvh {
 
 static_assert(KNN_MAX_K == BVH_KNN_MAX_K, "the largest bucket holds BVH_KNN_MAX_K entries");
 static_assert(sizeof(bvh_instance_knn_hit) == sizeof(uint4), "a record leaves in one 16-byte store");
-
-// the query point on the level the walk is on: the world point with e = 0, s2 = 1, or instance k's object-space point with its slack and scale bound
-struct SKPoint { QF3 p; float e, s2; };
 
 // one lane's list: kcol / pcol = its LDS columns (stride QUERY_BLOCK), cnt entries of k, (last, lastp) = the entry at place k-1 once cnt == k, bound = the
 // culling / acceptance bound: last's dist2 once the list is full, r2 before
@@ -56,36 +52,9 @@ __device__ __forceinline__ void sknn_insert(SKList& L, float d2, u32 inst, u32 p
     }
 }
 
-__device__ __forceinline__ bool sknn_box_dist_pass(const Box& b, const SKPoint& c, float bound, float& lb_out) {
-    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz))) + c.e;
-    const float dx = fmaxf(fmaxf((b.lx - g) - c.p.x, c.p.x - (b.hx + g)), 0.0f);
-    const float dy = fmaxf(fmaxf((b.ly - g) - c.p.y, c.p.y - (b.hy + g)), 0.0f);
-    const float dz = fmaxf(fmaxf((b.lz - g) - c.p.z, c.p.z - (b.hz + g)), 0.0f);
-    const float lb = (dx * dx + dy * dy) + dz * dz;
-    lb_out = lb;
-    return !((c.s2 * lb) * (1.0f - PQUERY_REL) > bound);         // (a NaN product never culls)
-}
-
-// the world point w in instance k's object space, with its slack, scale bound and BLAS; false: inactive instance
-__device__ __forceinline__ bool sknn_enter_instance(const SceneQuery& a, u32 k, QF3 w, SKPoint& c, SceneBlas& B) {
-    const float4* q = reinterpret_cast<const float4*>(a.inst + k);
-    const float4 q3 = q[3];
-    const u32 bl = __float_as_uint(q3.x);
-    if (bl == INV) return false;
-    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
-    const float m[12] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
-    B = a.blas[bl];
-    c.p = xf_point(m, w.x, w.y, w.z);
-    const float ax = fabsf(w.x), ay = fabsf(w.y), az = fabsf(w.z);
-    const float r0 = ((fabsf(m[0]) * ax + fabsf(m[1]) * ay) + fabsf(m[2]) * az) + fabsf(m[3]);
-    const float r1 = ((fabsf(m[4]) * ax + fabsf(m[5]) * ay) + fabsf(m[6]) * az) + fabsf(m[7]);
-    const float r2 = ((fabsf(m[8]) * ax + fabsf(m[9]) * ay) + fabsf(m[10]) * az) + fabsf(m[11]);
-    c.e = 0x1p-20f * fmaxf(fmaxf(r0, r1), r2);
-    c.s2 = q3.y;
-    return true;
-}
-
-// the candidate of (inst, prim): the world triangle's squared distance to the world point w, offered to the list
+// the candidate of (inst, prim): the world triangle's squared distance to the world point w, offered to the list.  The world triangle is blas_world_tri's
+// (scene_query.hpp) written out: through the shared helper the same operations were scheduled differently and k_scene_knn<32> measured 0.5 % slower on the
+// 64-instance scene (19.62 -> 19.73 ms per 2^20 points, four interleaved runs each, spread of either 0.4 %), so this leaf keeps the text it was measured with
 __device__ __forceinline__ void sknn_leaf(const SceneQuery& a, const SceneBlas& B, u32 prim, u32 inst, QF3 w, SKList& L) {
     if (prim >= B.n) return;
     const TriSrc src{ B.tris, reinterpret_cast<const float*>(B.tris), reinterpret_cast<const u32*>(B.idx), B.nv };
@@ -120,8 +89,8 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_knn(SceneQuery a) {
     SKList L{ s_key + tid_x(), s_prim + tid_x(), k, 0u, 0ull, INV, r2 };
     bool deep = false;
     if (live) {
-        const SKPoint world{ w, 0.0f, 1.0f };
-        SKPoint c = world;
+        const ScenePoint world{ w, 0.0f, 1.0f };
+        ScenePoint c = world;
         SceneBlas B{};
         const u32 tni = a.n_inst - 1, ttotal = 2 * a.n_inst - 1;
         u32 ni = tni, total = ttotal;                                 // of the level the query is on
@@ -130,7 +99,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_knn(SceneQuery a) {
         u32 nl = INV, nr = INV, top = 0, tsteps = 0, bsteps = 0;
         if (a.n_inst == 1) {                                          // no top-level tree: the instance's world box, then the instance
             float lb;
-            if (sknn_box_dist_pass(box_load(reinterpret_cast<const bvh_aabb*>(a.wbox)), world, L.bound, lb)) { enter = 0; entering = true; } else pop = true;
+            if (scene_box_dist_pass(box_load(reinterpret_cast<const bvh_aabb*>(a.wbox)), world, L.bound, lb)) { enter = 0; entering = true; } else pop = true;
         } else {
             const uint2 lr = *reinterpret_cast<const uint2*>(reinterpret_cast<const bvh2_node*>(a.tnodes) + a.troot); nl = lr.x; nr = lr.y;
         }
@@ -138,7 +107,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_knn(SceneQuery a) {
             if (entering) {
                 entering = false;
                 const u32 e = enter;
-                if (e < a.n_inst && sknn_enter_instance(a, e, w, c, B)) {
+                if (e < a.n_inst && enter_instance_point(a, e, w, c, B)) {
                     in_blas = true; inst = e; ni = B.n - 1; total = 2 * B.n - 1; bsteps = 0;
                     const uint2 lr = *reinterpret_cast<const uint2*>(reinterpret_cast<const bvh2_node*>(B.nodes) + B.root); nl = lr.x; nr = lr.y;
                 } else pop = true;
@@ -151,8 +120,8 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_knn(SceneQuery a) {
                 Box ba, bb;
                 float la = 0.0f, lb = 0.0f;
                 bool ha = false, hb = false;
-                if (nl < total) { rec_fetch_rt(layout, nodes, leaves, nl, ni, a0, a1, ba); ha = sknn_box_dist_pass(ba, c, L.bound, la); }
-                if (nr < total) { rec_fetch_rt(layout, nodes, leaves, nr, ni, b0, b1, bb); hb = sknn_box_dist_pass(bb, c, L.bound, lb); }
+                if (nl < total) { rec_fetch_rt(layout, nodes, leaves, nl, ni, a0, a1, ba); ha = scene_box_dist_pass(ba, c, L.bound, la); }
+                if (nr < total) { rec_fetch_rt(layout, nodes, leaves, nr, ni, b0, b1, bb); hb = scene_box_dist_pass(bb, c, L.bound, lb); }
                 if (in_blas) {                                        // triangles at once; at the top level a leaf is an instance, entered like a node
                     if (ha && nl >= ni) { sknn_leaf(a, B, a0, inst, w, L); ha = false; }
                     if (hb && nr >= ni) { sknn_leaf(a, B, b0, inst, w, L); hb = false; }
@@ -207,8 +176,8 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_knn(SceneQuery a) {
 
 // stackless walk of instance k's BLAS (k_scene_closest_point_deep's walk through the BLAS's plan)
 __device__ void sknn_walk_blas(const SceneQuery& a, u32 k, QF3 w, SKList& L) {
-    SKPoint c; SceneBlas B;
-    if (k >= a.n_inst || !sknn_enter_instance(a, k, w, c, B)) return;
+    ScenePoint c; SceneBlas B;
+    if (k >= a.n_inst || !enter_instance_point(a, k, w, c, B)) return;
     const u32 ni = B.n - 1, total = 2 * B.n - 1;
     const u64 bound = 3ull * total + 3ull;
     u32 cur = B.root, last = INV;
@@ -218,7 +187,7 @@ __device__ void sknn_walk_blas(const SceneQuery& a, u32 k, QF3 w, SKList& L) {
         if (down) {
             rec_fetch_rt((int)B.layout, B.nodes, B.leaves, cur, ni, w0, w1, b);
             float lb;
-            const bool pass = sknn_box_dist_pass(b, c, L.bound, lb);
+            const bool pass = scene_box_dist_pass(b, c, L.bound, lb);
             if (cur >= ni) {
                 if (pass) sknn_leaf(a, B, w0, k, w, L);
                 last = cur; cur = B.parent[cur]; down = false;
@@ -249,11 +218,11 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_knn_deep(SceneQuery a) {
         if (mine->prim_idx != QUERY_MARK) continue;
         QF3 w; float r2;
         point_load(reinterpret_cast<const bvh_point_query*>(a.rays), i, w, r2);   // (a marked query passed the checks)
-        const SKPoint world{ w, 0.0f, 1.0f };
+        const ScenePoint world{ w, 0.0f, 1.0f };
         SKList L{ s_key + tid_x(), s_prim + tid_x(), k, 0u, 0ull, INV, r2 };
         if (a.n_inst == 1) {
             float lb;
-            if (sknn_box_dist_pass(box_load(reinterpret_cast<const bvh_aabb*>(a.wbox)), world, L.bound, lb)) sknn_walk_blas(a, 0, w, L);
+            if (scene_box_dist_pass(box_load(reinterpret_cast<const bvh_aabb*>(a.wbox)), world, L.bound, lb)) sknn_walk_blas(a, 0, w, L);
         } else {
             u32 cur = a.troot, last = INV;
             bool down = true;
@@ -262,7 +231,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_knn_deep(SceneQuery a) {
                 if (down) {
                     rec_fetch_rt((int)a.tlayout, a.tnodes, a.tleaves, cur, tni, w0, w1, b);
                     float lb;
-                    if (!sknn_box_dist_pass(b, world, L.bound, lb)) { last = cur; cur = a.tparent[cur]; down = false; continue; }
+                    if (!scene_box_dist_pass(b, world, L.bound, lb)) { last = cur; cur = a.tparent[cur]; down = false; continue; }
                     if (cur >= tni) {                                 // an instance whose world box passes
                         sknn_walk_blas(a, w0, w, L);
                         last = cur; cur = a.tparent[cur]; down = false;

@@ -1,19 +1,15 @@
 // scene_map.hpp — what the set-valued scene queries that test MAPPED boxes share (scene_overlap.hip: bvh_scene_overlap; scene_tris.hip:
-// bvh_scene_intersect_tris; scene_collide.hip: bvh_scene_collide): the forward matrix of the entered instance, the header's mapped box, the
+// bvh_scene_intersect_tris; scene_collide.hip: bvh_scene_collide): the forward matrix of the entered instance (SOMat, scene_query.hpp), the header's mapped box, the
 // record sink and, for the two crossing-pair files, the world triangle of an instance's primitive.
 //   mapped(M, {lo, hi}), row r:  a_c = m_rc * lo.c, b_c = m_rc * hi.c,  min.r = ((fminf(a_0, b_0) + fminf(a_1, b_1)) + fminf(a_2, b_2)) + m_r3,  max.r with fmaxf
 // in f32 without contraction (every file that includes this is built with -ffp-contract=off and without the SLP vectoriser, Makefile).
 #pragma once
-#include "query.hpp"
+#include "scene_query.hpp"
 #include "tri_cross.hpp"
-#include "kernels.hpp"
 
 namespace bvh {
 
 static_assert(sizeof(bvh_instance_prim) == sizeof(uint2), "a record leaves in one 8-byte store");
-
-// the forward matrix of the instance the walk is in (rows of object_to_world)
-struct SOMat { float4 r0, r1, r2; };
 
 // where a walk's records go (overlap.hip's Sink for bvh_instance_prim records {prim, instance})
 template <bool FILL, bool SORTED> struct SceneOverlapSink {
@@ -55,8 +51,7 @@ __device__ __forceinline__ bool sov_box_pass(const Box& q, const SOMat& M, const
 __device__ __forceinline__ bool sov_enter_instance(const SceneQuery& a, u32 k, SOMat& M, SceneBlas& B) {
     const u32 bl = __float_as_uint(reinterpret_cast<const float4*>(a.inst + k)[3].x);
     if (bl == INV) return false;
-    const float4* mq = reinterpret_cast<const float4*>(reinterpret_cast<const bvh_instance*>(a.inst_in) + k);
-    M.r0 = mq[0]; M.r1 = mq[1]; M.r2 = mq[2];
+    M = inst_load_m(a, k);
     B = a.blas[bl];
     return true;
 }
@@ -69,9 +64,8 @@ __device__ __forceinline__ QF3 st_world(const SOMat& M, QF3 v) {
 
 // the world triangle of primitive prim (< B.n) of the instance whose matrix is M
 __device__ __forceinline__ void st_world_tri(const SceneBlas& B, const SOMat& M, u32 prim, QF3& y1, QF3& y2, QF3& y3) {
-    const TriSrc src{ B.tris, reinterpret_cast<const float*>(B.tris), reinterpret_cast<const u32*>(B.idx), B.nv };
     QF3 v1, v2, v3;
-    tt_query_fetch((int)B.fmt, src, prim, v1, v2, v3);
+    blas_tri_fetch(B, prim, v1, v2, v3);
     y1 = st_world(M, v1); y2 = st_world(M, v2); y3 = st_world(M, v3);
 }
 

@@ -1,6 +1,6 @@
 // scene_multihit.hip — bvh_scene_intersect_all on gfx950: EVERY accepted hit along each ray over all active instances of a scene (no counterpart in the
 // reference).  The two-level walk is scene.hip's (one ray per lane, one LDS short stack shared by both levels, the BLAS's layout and format dispatched at run
-// time from its descriptor), the count -> scan -> fill scheme is multihit.hip's, and the differences from k_scene_intersect are those between k_hits_walk and
+// time from its descriptor, entered through scene_query.hpp's enter_instance_ray), the count -> scan -> fill scheme is multihit.hip's, and the differences from k_scene_intersect are those between k_hits_walk and
 // k_intersect: box_pass runs against the ray's tmax for the whole walk, a passing BLAS leaf child is hit-tested at once and handed to the sink, and of two
 // passing children the left one is entered and the right one pushed.  DESIGN.md §8o.
 //   k_scene_hits_walk : count pass (FILL = false: d_offsets[i] = ray i's number of accepted hits) and fill pass (FILL = true: the records go to the ray's slice).
@@ -15,8 +15,7 @@
 // (t, instance, prim) order by comparing and shifting whole records from its tail; inside one instance the earlier hits of that instance are already there and
 // across instances the keys interleave, so the instance index takes part in the comparison.
 // Compiled WITHOUT the SLP vectoriser (Makefile), like scene.hip and multihit.hip: the sorted insertion compares and replaces records.
-#include "query.hpp"
-#include "kernels.hpp"
+#include "scene_query.hpp"
 
 namespace bvh {
 
@@ -43,31 +42,12 @@ template <bool FILL, bool SORTED> struct SceneHitSink {
     }
 };
 
-// the world ray w in instance k's object space (tmin / tmax kept); false: inactive instance.  scene.hip's enter_instance, word for word
-__device__ __forceinline__ bool hits_enter_instance(const SceneQuery& a, u32 k, const QRay& w, QRay& r, SceneBlas& B) {
-    const float4* q = reinterpret_cast<const float4*>(a.inst + k);
-    const u32 bl = __float_as_uint(q[3].x);
-    if (bl == INV) return false;
-    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
-    const float m[12] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
-    B = a.blas[bl];
-    r.o = xf_point(m, w.o.x, w.o.y, w.o.z);
-    r.d = { (m[0] * w.d.x + m[1] * w.d.y) + m[2] * w.d.z, (m[4] * w.d.x + m[5] * w.d.y) + m[6] * w.d.z, (m[8] * w.d.x + m[9] * w.d.y) + m[10] * w.d.z };
-    r.inv = { 1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z };
-    r.nx = __float_as_uint(r.d.x) >> 31; r.ny = __float_as_uint(r.d.y) >> 31; r.nz = __float_as_uint(r.d.z) >> 31;
-    r.tmin = w.tmin; r.tmax = w.tmax;
-    return true;
-}
-
 // the candidate prim's test with the BLAS's format chosen at run time: in range (never followed otherwise) and an accepted hit
 template <bool FILL, bool SORTED>
 __device__ __forceinline__ void scene_hit_leaf(const SceneBlas& B, u32 prim, u32 inst, const QRay& r, SceneHitSink<FILL, SORTED>& sink) {
     if (prim >= B.n) return;
-    const TriSrc src{ B.tris, reinterpret_cast<const float*>(B.tris), reinterpret_cast<const u32*>(B.idx), B.nv };
     QF3 a, b, c;
-    if (B.fmt == BVH_TRI_PADDED64) tri_fetch<BVH_TRI_PADDED64>(src, prim, a, b, c);
-    else if (B.fmt == BVH_TRI_PACKED36) tri_fetch<BVH_TRI_PACKED36>(src, prim, a, b, c);
-    else tri_fetch<BVH_TRI_INDEXED>(src, prim, a, b, c);
+    blas_tri_fetch(B, prim, a, b, c);
     float it = 0.0f, iu = 0.0f, iv = 0.0f;
     if (tri_hit(a, b, c, r, it, iu, iv) && r.tmin < it && it < r.tmax) sink.put(it, iu, iv, prim, inst);
 }
@@ -106,7 +86,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_hits_walk(SceneQuery a, S
             if (entering) {
                 entering = false;
                 const u32 k = enter;
-                if (k < a.n_inst && hits_enter_instance(a, k, w, r, B)) {
+                if (k < a.n_inst && enter_instance_ray(a, k, w, r, B)) {
                     in_blas = true; inst = k; ni = B.n - 1; total = 2 * B.n - 1; bsteps = 0;
                     const uint2 lr = *reinterpret_cast<const uint2*>(reinterpret_cast<const bvh2_node*>(B.nodes) + B.root); nl = lr.x; nr = lr.y;
                 } else pop = true;
@@ -159,7 +139,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_hits_walk(SceneQuery a, S
 template <bool FILL, bool SORTED>
 __device__ void scene_hits_walk_blas(const SceneQuery& a, u32 k, const QRay& w, SceneHitSink<FILL, SORTED>& sink) {
     QRay r; SceneBlas B;
-    if (k >= a.n_inst || !hits_enter_instance(a, k, w, r, B)) return;
+    if (k >= a.n_inst || !enter_instance_ray(a, k, w, r, B)) return;
     const u32 ni = B.n - 1, total = 2 * B.n - 1;
     const u64 bound = 3ull * total + 3ull;
     u32 cur = B.root, last = INV;

@@ -11,60 +11,23 @@
 //                                levels, leaf children whose box passes tested at once.  The forward matrix is re-loaded per leaf test from the scene's copy of
 //                                the caller's records (12 floats that L2 serves; keeping them live across the BLAS walk would cost 12 VGPRs all the way).
 //   k_scene_closest_point_deep : the marked queries, stackless: the top-level plan, and for every instance whose world box passes, that BLAS's plan.
+// The box test (scene_box_dist_pass), the entry into an instance (enter_instance_point) and the world triangle (blas_world_tri) are scene_query.hpp's, shared
+// with scene_knn.hip (the first two) and scene_radius.hip.
 // Built without the SLP vectoriser (Makefile), as scene.o and point_query.o: the record update is the same tie-breaking pattern.
-#include "query.hpp"
-#include "kernels.hpp"
+#include "scene_query.hpp"
 
 namespace bvh {
 
 // the best candidate so far: world closest point, world dist2, weights, prim and instance (INV: none)
 struct SPBest { QF3 q; float d2, u, v; u32 prim, inst; };
-// the query point on the level the walk is on: the world point with e = 0, s2 = 1, or instance k's object-space point with its slack and scale bound
-struct SPoint { QF3 p; float e, s2; };
-
-__device__ __forceinline__ bool scene_box_dist_pass(const Box& b, const SPoint& c, float best, float& lb_out) {
-    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz))) + c.e;
-    const float dx = fmaxf(fmaxf((b.lx - g) - c.p.x, c.p.x - (b.hx + g)), 0.0f);
-    const float dy = fmaxf(fmaxf((b.ly - g) - c.p.y, c.p.y - (b.hy + g)), 0.0f);
-    const float dz = fmaxf(fmaxf((b.lz - g) - c.p.z, c.p.z - (b.hz + g)), 0.0f);
-    const float lb = (dx * dx + dy * dy) + dz * dz;
-    lb_out = lb;
-    return !((c.s2 * lb) * (1.0f - PQUERY_REL) > best);          // (a NaN product never culls)
-}
-
-// the world point w in instance k's object space, with its slack, scale bound and BLAS; false: inactive instance
-__device__ __forceinline__ bool enter_instance_point(const SceneQuery& a, u32 k, QF3 w, SPoint& c, SceneBlas& B) {
-    const float4* q = reinterpret_cast<const float4*>(a.inst + k);
-    const float4 q3 = q[3];
-    const u32 bl = __float_as_uint(q3.x);
-    if (bl == INV) return false;
-    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
-    const float m[12] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
-    B = a.blas[bl];
-    c.p = xf_point(m, w.x, w.y, w.z);
-    const float ax = fabsf(w.x), ay = fabsf(w.y), az = fabsf(w.z);
-    const float r0 = ((fabsf(m[0]) * ax + fabsf(m[1]) * ay) + fabsf(m[2]) * az) + fabsf(m[3]);
-    const float r1 = ((fabsf(m[4]) * ax + fabsf(m[5]) * ay) + fabsf(m[6]) * az) + fabsf(m[7]);
-    const float r2 = ((fabsf(m[8]) * ax + fabsf(m[9]) * ay) + fabsf(m[10]) * az) + fabsf(m[11]);
-    c.e = 0x1p-20f * fmaxf(fmaxf(r0, r1), r2);
-    c.s2 = q3.y;
-    return true;
-}
 
 // the candidate of (inst, prim): the world triangle's closest point to the world point w; the record update in the order (dist2, instance, prim).  best starts
 // at {r2, INV, INV}, so the comparison is also the acceptance test d2 <= r2 (NaN fails both).  True when an any-hit query is done.
 template <int QUERY>
 __device__ __forceinline__ bool scene_leaf_point(const SceneQuery& a, const SceneBlas& B, u32 prim, u32 inst, QF3 w, SPBest& best) {
     if (prim >= B.n) return false;
-    const TriSrc src{ B.tris, reinterpret_cast<const float*>(B.tris), reinterpret_cast<const u32*>(B.idx), B.nv };
-    QF3 v1, v2, v3;
-    if (B.fmt == BVH_TRI_PADDED64) tri_fetch<BVH_TRI_PADDED64>(src, prim, v1, v2, v3);
-    else if (B.fmt == BVH_TRI_PACKED36) tri_fetch<BVH_TRI_PACKED36>(src, prim, v1, v2, v3);
-    else tri_fetch<BVH_TRI_INDEXED>(src, prim, v1, v2, v3);
-    const float4* mq = reinterpret_cast<const float4*>(reinterpret_cast<const bvh_instance*>(a.inst_in) + inst);
-    const float4 m0 = mq[0], m1 = mq[1], m2 = mq[2];
-    const float m[12] = { m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w };
-    const QF3 wa = xf_point(m, v1.x, v1.y, v1.z), wb = xf_point(m, v2.x, v2.y, v2.z), wc = xf_point(m, v3.x, v3.y, v3.z);
+    QF3 wa, wb, wc;
+    blas_world_tri(a, B, prim, inst, wa, wb, wc);
     QF3 q; float u, v;
     const float d2 = tri_closest(wa, wb, wc, w, q, u, v);
     if (!(d2 < best.d2 || (d2 == best.d2 && (inst < best.inst || (inst == best.inst && prim < best.prim))))) return false;
@@ -90,8 +53,8 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_closest_point(SceneQuery 
     SPBest best{ { 0.0f, 0.0f, 0.0f }, r2, 0.0f, 0.0f, INV, INV };
     bool deep = false;
     if (live) {
-        const SPoint world{ w, 0.0f, 1.0f };
-        SPoint c = world;
+        const ScenePoint world{ w, 0.0f, 1.0f };
+        ScenePoint c = world;
         SceneBlas B{};
         const u32 tni = a.n_inst - 1, ttotal = 2 * a.n_inst - 1;
         u32 ni = tni, total = ttotal;                                 // of the level the query is on
@@ -165,7 +128,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_closest_point(SceneQuery 
 // stackless walk of instance k's BLAS (k_closest_point_deep's walk through the BLAS's plan); true when an any-hit query is done
 template <int QUERY>
 __device__ bool scene_point_walk_blas(const SceneQuery& a, u32 k, QF3 w, SPBest& best) {
-    SPoint c; SceneBlas B;
+    ScenePoint c; SceneBlas B;
     if (k >= a.n_inst || !enter_instance_point(a, k, w, c, B)) return false;
     const u32 ni = B.n - 1, total = 2 * B.n - 1;
     const u64 bound = 3ull * total + 3ull;
@@ -204,7 +167,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_closest_point_deep(SceneQ
         if (reinterpret_cast<const u32*>(a.hits)[8 * (size_t)i + 6] != QUERY_MARK) continue;
         QF3 w; float r2;
         point_load(reinterpret_cast<const bvh_point_query*>(a.rays), i, w, r2);   // (a marked query passed the checks)
-        const SPoint world{ w, 0.0f, 1.0f };
+        const ScenePoint world{ w, 0.0f, 1.0f };
         SPBest best{ { 0.0f, 0.0f, 0.0f }, r2, 0.0f, 0.0f, INV, INV };
         if (a.n_inst == 1) {
             float lb;

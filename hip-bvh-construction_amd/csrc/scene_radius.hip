@@ -1,7 +1,7 @@
 // scene_radius.hip — bvh_scene_radius_search on gfx950: EVERY triangle within the radius of each query point, over all active instances of a scene (no
 // counterpart in the reference).  The two-level point walk is scene_knn.hip's (one query per lane, one LDS short stack shared by both levels, the candidate of
 // (instance k, primitive j) is tri_closest on the WORLD triangle, the walk inside an instance runs in object space against the mapped point p' = W_k p with the
-// box grown by QUERY_GROW * (its largest |coordinate|) + e and culled iff s2 * lb' * (1 - 2^-20) > bound: DESIGN.md §8n), the count -> scan -> fill scheme is
+// box grown by QUERY_GROW * (its largest |coordinate|) + e and culled iff s2 * lb' * (1 - 2^-20) > bound: DESIGN.md §8n, scene_query.hpp), the count -> scan -> fill scheme is
 // radius.hip's and scene_multihit.hip's, and what differs from k_scene_knn is what differs between k_radius_walk and k_knn: the bound never shrinks — the box
 // test runs against r2 for the whole walk — so every passing subtree is visited, of two passing children the left one is entered and the right one pushed, and
 // the answer is a set of {dist2, prim, instance} records.  DESIGN.md §8q.
@@ -19,15 +19,11 @@
 // then the prim: an accepted dist2 is a sum of squares, never negative and never NaN, so that is the contract's lexicographic order.  The insertion is quadratic
 // in the slice's length.
 // Compiled WITHOUT the SLP vectoriser (Makefile), like scene_knn.hip and scene_multihit.hip: the sorted insertion compares and replaces records.
-#include "query.hpp"
-#include "kernels.hpp"
+#include "scene_query.hpp"
 
 namespace bvh {
 
 static_assert(sizeof(bvh_instance_knn_hit) == sizeof(uint4), "a record leaves in one 16-byte store");
-
-// the query point on the level the walk is on: the world point with e = 0, s2 = 1, or instance k's object-space point with its slack and scale bound
-struct SRPoint { QF3 p; float e, s2; };
 
 // where a walk's records go (radius.hip's RadiusSink for bvh_instance_knn_hit records {dist2 bits, prim, instance, 0})
 template <bool FILL, bool SORTED> struct SceneRadiusSink {
@@ -53,49 +49,13 @@ template <bool FILL, bool SORTED> struct SceneRadiusSink {
     }
 };
 
-// scene_knn.hip's sknn_box_dist_pass
-__device__ __forceinline__ bool srad_box_dist_pass(const Box& b, const SRPoint& c, float bound) {
-    const float g = QUERY_GROW * fmaxf(fmaxf(fmaxf(fabsf(b.lx), fabsf(b.hx)), fmaxf(fabsf(b.ly), fabsf(b.hy))), fmaxf(fabsf(b.lz), fabsf(b.hz))) + c.e;
-    const float dx = fmaxf(fmaxf((b.lx - g) - c.p.x, c.p.x - (b.hx + g)), 0.0f);
-    const float dy = fmaxf(fmaxf((b.ly - g) - c.p.y, c.p.y - (b.hy + g)), 0.0f);
-    const float dz = fmaxf(fmaxf((b.lz - g) - c.p.z, c.p.z - (b.hz + g)), 0.0f);
-    const float lb = (dx * dx + dy * dy) + dz * dz;
-    return !((c.s2 * lb) * (1.0f - PQUERY_REL) > bound);         // (a NaN product never culls)
-}
-
-// the world point w in instance k's object space, with its slack, scale bound and BLAS; false: inactive instance.  scene_knn.hip's sknn_enter_instance
-__device__ __forceinline__ bool srad_enter_instance(const SceneQuery& a, u32 k, QF3 w, SRPoint& c, SceneBlas& B) {
-    const float4* q = reinterpret_cast<const float4*>(a.inst + k);
-    const float4 q3 = q[3];
-    const u32 bl = __float_as_uint(q3.x);
-    if (bl == INV) return false;
-    const float4 q0 = q[0], q1 = q[1], q2 = q[2];
-    const float m[12] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
-    B = a.blas[bl];
-    c.p = xf_point(m, w.x, w.y, w.z);
-    const float ax = fabsf(w.x), ay = fabsf(w.y), az = fabsf(w.z);
-    const float r0 = ((fabsf(m[0]) * ax + fabsf(m[1]) * ay) + fabsf(m[2]) * az) + fabsf(m[3]);
-    const float r1 = ((fabsf(m[4]) * ax + fabsf(m[5]) * ay) + fabsf(m[6]) * az) + fabsf(m[7]);
-    const float r2 = ((fabsf(m[8]) * ax + fabsf(m[9]) * ay) + fabsf(m[10]) * az) + fabsf(m[11]);
-    c.e = 0x1p-20f * fmaxf(fmaxf(r0, r1), r2);
-    c.s2 = q3.y;
-    return true;
-}
-
 // the candidate of (inst, prim): the world triangle's squared distance to the world point w, accepted iff dist2 <= r2 (a NaN dist2 fails).  The forward
-// matrix is re-loaded per leaf test (sknn_leaf): it never lives across the walk
+// matrix is re-loaded per leaf test (blas_world_tri): it never lives across the walk
 template <bool FILL, bool SORTED>
 __device__ __forceinline__ void srad_leaf(const SceneQuery& a, const SceneBlas& B, u32 prim, u32 inst, QF3 w, float r2, SceneRadiusSink<FILL, SORTED>& sink) {
     if (prim >= B.n) return;
-    const TriSrc src{ B.tris, reinterpret_cast<const float*>(B.tris), reinterpret_cast<const u32*>(B.idx), B.nv };
-    QF3 v1, v2, v3;
-    if (B.fmt == BVH_TRI_PADDED64) tri_fetch<BVH_TRI_PADDED64>(src, prim, v1, v2, v3);
-    else if (B.fmt == BVH_TRI_PACKED36) tri_fetch<BVH_TRI_PACKED36>(src, prim, v1, v2, v3);
-    else tri_fetch<BVH_TRI_INDEXED>(src, prim, v1, v2, v3);
-    const float4* mq = reinterpret_cast<const float4*>(reinterpret_cast<const bvh_instance*>(a.inst_in) + inst);
-    const float4 m0 = mq[0], m1 = mq[1], m2 = mq[2];
-    const float m[12] = { m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w };
-    const QF3 wa = xf_point(m, v1.x, v1.y, v1.z), wb = xf_point(m, v2.x, v2.y, v2.z), wc = xf_point(m, v3.x, v3.y, v3.z);
+    QF3 wa, wb, wc;
+    blas_world_tri(a, B, prim, inst, wa, wb, wc);
     QF3 q; float u, v;
     const float d2 = tri_closest(wa, wb, wc, w, q, u, v);
     if (d2 <= r2) sink.put(d2, prim, inst);
@@ -118,8 +78,8 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_radius_walk(SceneQuery a,
     const bool live = point_load(reinterpret_cast<const bvh_point_query*>(a.rays), i, w, r2);
     bool deep = false;
     if (live) {                                                   // (a NaN coordinate, a NaN or negative radius: accepts nothing)
-        const SRPoint world{ w, 0.0f, 1.0f };
-        SRPoint c = world;
+        const ScenePoint world{ w, 0.0f, 1.0f };
+        ScenePoint c = world;
         SceneBlas B{};
         const u32 tni = a.n_inst - 1, ttotal = 2 * a.n_inst - 1;
         u32 ni = tni, total = ttotal;                                 // of the level the query is on
@@ -127,7 +87,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_radius_walk(SceneQuery a,
         u32 inst = INV, enter = INV;
         u32 nl = INV, nr = INV, top = 0, tsteps = 0, bsteps = 0;
         if (a.n_inst == 1) {                                          // no top-level tree: the instance's world box, then the instance
-            if (srad_box_dist_pass(box_load(reinterpret_cast<const bvh_aabb*>(a.wbox)), world, r2)) { enter = 0; entering = true; } else pop = true;
+            if (scene_box_dist_pass(box_load(reinterpret_cast<const bvh_aabb*>(a.wbox)), world, r2)) { enter = 0; entering = true; } else pop = true;
         } else {
             const uint2 lr = *reinterpret_cast<const uint2*>(reinterpret_cast<const bvh2_node*>(a.tnodes) + a.troot); nl = lr.x; nr = lr.y;
         }
@@ -135,7 +95,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_radius_walk(SceneQuery a,
             if (entering) {
                 entering = false;
                 const u32 k = enter;
-                if (k < a.n_inst && srad_enter_instance(a, k, w, c, B)) {
+                if (k < a.n_inst && enter_instance_point(a, k, w, c, B)) {
                     in_blas = true; inst = k; ni = B.n - 1; total = 2 * B.n - 1; bsteps = 0;
                     const uint2 lr = *reinterpret_cast<const uint2*>(reinterpret_cast<const bvh2_node*>(B.nodes) + B.root); nl = lr.x; nr = lr.y;
                 } else pop = true;
@@ -147,8 +107,8 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_radius_walk(SceneQuery a,
                 u32 a0 = INV, a1 = INV, b0 = INV, b1 = INV;
                 Box ba, bb;
                 bool ha = false, hb = false;
-                if (nl < total) { rec_fetch_rt(layout, nodes, leaves, nl, ni, a0, a1, ba); ha = srad_box_dist_pass(ba, c, r2); }
-                if (nr < total) { rec_fetch_rt(layout, nodes, leaves, nr, ni, b0, b1, bb); hb = srad_box_dist_pass(bb, c, r2); }
+                if (nl < total) { rec_fetch_rt(layout, nodes, leaves, nl, ni, a0, a1, ba); ha = scene_box_dist_pass(ba, c, r2); }
+                if (nr < total) { rec_fetch_rt(layout, nodes, leaves, nr, ni, b0, b1, bb); hb = scene_box_dist_pass(bb, c, r2); }
                 if (in_blas) {                                        // triangles at once; at the top level a leaf is an instance, entered like a node
                     if (ha && nl >= ni) { srad_leaf(a, B, a0, inst, w, r2, sink); ha = false; }
                     if (hb && nr >= ni) { srad_leaf(a, B, b0, inst, w, r2, sink); hb = false; }
@@ -187,8 +147,8 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_radius_walk(SceneQuery a,
 // is not tested, every other record's is)
 template <bool FILL, bool SORTED>
 __device__ void srad_walk_blas(const SceneQuery& a, u32 k, QF3 w, float r2, SceneRadiusSink<FILL, SORTED>& sink) {
-    SRPoint c; SceneBlas B;
-    if (k >= a.n_inst || !srad_enter_instance(a, k, w, c, B)) return;
+    ScenePoint c; SceneBlas B;
+    if (k >= a.n_inst || !enter_instance_point(a, k, w, c, B)) return;
     const u32 ni = B.n - 1, total = 2 * B.n - 1;
     const u64 bound = 3ull * total + 3ull;
     u32 cur = B.root, last = INV;
@@ -198,11 +158,11 @@ __device__ void srad_walk_blas(const SceneQuery& a, u32 k, QF3 w, float r2, Scen
             u32 w0, w1; Box b;
             rec_fetch_rt((int)B.layout, B.nodes, B.leaves, cur, ni, w0, w1, b);
             if (cur >= ni) {
-                if (srad_box_dist_pass(b, c, r2)) srad_leaf(a, B, w0, k, w, r2, sink);
+                if (scene_box_dist_pass(b, c, r2)) srad_leaf(a, B, w0, k, w, r2, sink);
                 last = cur; cur = B.parent[cur]; down = false;
                 continue;
             }
-            if (cur != B.root && !srad_box_dist_pass(b, c, r2)) { last = cur; cur = B.parent[cur]; down = false; continue; }   // (the BLAS root's own box: as the stack walk, not tested)
+            if (cur != B.root && !scene_box_dist_pass(b, c, r2)) { last = cur; cur = B.parent[cur]; down = false; continue; }   // (the BLAS root's own box: as the stack walk, not tested)
             if (w0 < total) { cur = w0; continue; }
             last = w0; down = false;                              // (a left link out of range: as if its subtree were done)
             continue;
@@ -231,9 +191,9 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_radius_deep(SceneQuery a,
         } else if (h.offsets[i] != QUERY_MARK) continue;
         QF3 w; float r2;
         point_load(reinterpret_cast<const bvh_point_query*>(a.rays), i, w, r2);   // (a marked query passed the checks)
-        const SRPoint world{ w, 0.0f, 1.0f };
+        const ScenePoint world{ w, 0.0f, 1.0f };
         if (a.n_inst == 1) {
-            if (srad_box_dist_pass(box_load(reinterpret_cast<const bvh_aabb*>(a.wbox)), world, r2)) srad_walk_blas(a, 0, w, r2, sink);
+            if (scene_box_dist_pass(box_load(reinterpret_cast<const bvh_aabb*>(a.wbox)), world, r2)) srad_walk_blas(a, 0, w, r2, sink);
         } else {
             u32 cur = a.troot, last = INV;
             bool down = true;
@@ -241,7 +201,7 @@ __global__ __launch_bounds__(QUERY_BLOCK) void k_scene_radius_deep(SceneQuery a,
                 if (down) {
                     u32 w0, w1; Box b;
                     rec_fetch_rt((int)a.tlayout, a.tnodes, a.tleaves, cur, tni, w0, w1, b);
-                    if (cur != a.troot && !srad_box_dist_pass(b, world, r2)) { last = cur; cur = a.tparent[cur]; down = false; continue; }   // (the root's own box: as the stack walk, not tested)
+                    if (cur != a.troot && !scene_box_dist_pass(b, world, r2)) { last = cur; cur = a.tparent[cur]; down = false; continue; }   // (the root's own box: as the stack walk, not tested)
                     if (cur >= tni) {                                 // an instance whose world box passes
                         srad_walk_blas(a, w0, w, r2, sink);
                         last = cur; cur = a.tparent[cur]; down = false;

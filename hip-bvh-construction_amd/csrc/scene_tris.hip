@@ -34,7 +34,7 @@ struct STQuery { TriSrc src; int fmt; u32 inst; };
 // query triangle i; false: the row is empty (INSTANCE mode: an inactive or out-of-range query instance, a row at or beyond its BLAS's n)
 template <int MODE>
 __device__ __forceinline__ bool st_query(const SceneQuery& a, const STQuery& t, u32 i, QF3& x1, QF3& x2, QF3& x3) {
-    if (MODE == BVH_SCENE_TRIS_QUERY) { tt_query_fetch(t.fmt, t.src, i, x1, x2, x3); return true; }
+    if (MODE == BVH_SCENE_TRIS_QUERY) { tri_fetch_rt(t.fmt, t.src, i, x1, x2, x3); return true; }
     SOMat M; SceneBlas B;
     if (t.inst >= a.n_inst || !sov_enter_instance(a, t.inst, M, B) || i >= B.n) return false;
     st_world_tri(B, M, i, x1, x2, x3);

@@ -19,7 +19,7 @@
 // two 64-byte records, no scratch either way, and the kernel's occupancy is set by the 16 KiB stack (3 waves per SIMD) in both — DESIGN.md §8w.
 // Built without the SLP vectoriser and without -fno-honor-nans (Makefile), as winding.o: the opening test must be false on NaN.
 #include "winding.hpp"
-#include "kernels.hpp"
+#include "scene_query.hpp"
 
 namespace bvh {
 
@@ -31,13 +31,6 @@ __device__ __forceinline__ u32 wind_find_blas(const u32* __restrict__ first, u32
         if (first[mid] <= t) lo = mid; else hi = mid;
     }
     return lo;
-}
-// tri_fetch with the BLAS's format chosen at run time
-__device__ __forceinline__ void blas_tri_fetch(const SceneBlas& B, u32 prim, QF3& a, QF3& b, QF3& c) {
-    const TriSrc src{ B.tris, reinterpret_cast<const float*>(B.tris), reinterpret_cast<const u32*>(B.idx), B.nv };
-    if (B.fmt == BVH_TRI_PADDED64) tri_fetch<BVH_TRI_PADDED64>(src, prim, a, b, c);
-    else if (B.fmt == BVH_TRI_PACKED36) tri_fetch<BVH_TRI_PACKED36>(src, prim, a, b, c);
-    else tri_fetch<BVH_TRI_INDEXED>(src, prim, a, b, c);
 }
 __device__ __forceinline__ u32 blas_leaf_prim(const SceneBlas& B, u32 c) {
     const u32 ni = B.n - 1;
@@ -133,9 +126,8 @@ __global__ __launch_bounds__(WIND_BLOCK) void k_scene_winding_inst(SceneQuery a,
     const u32 bl = a.inst[k].blas;
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (bl == INV) { mo[0] = zero; mo[1] = zero; mo[2] = zero; mo[3] = zero; io[0] = zero; io[1] = zero; return; }
-    const float4* mq = reinterpret_cast<const float4*>(reinterpret_cast<const bvh_instance*>(a.inst_in) + k);
-    const float4 m0 = mq[0], m1 = mq[1], m2 = mq[2];
-    const float m[12] = { m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w };
+    float m[12];
+    mat_rows(inst_load_m(a, k), m);
     const double a00 = m[0], a01 = m[1], a02 = m[2], a10 = m[4], a11 = m[5], a12 = m[6], a20 = m[8], a21 = m[9], a22 = m[10];
     const float c[9] = { (float)(a11 * a22 - a12 * a21), (float)(a12 * a20 - a10 * a22), (float)(a10 * a21 - a11 * a20),
                          (float)(a02 * a21 - a01 * a22), (float)(a00 * a22 - a02 * a20), (float)(a01 * a20 - a00 * a21),
@@ -164,11 +156,6 @@ __global__ __launch_bounds__(WIND_BLOCK) void k_scene_winding_inst(SceneQuery a,
 // what a walk knows of the instance it is in: the BLAS, its moments, the instance index and the 22 values of its maps (M, C, smax), live while it is inside
 struct WInst { SceneBlas B; const bvh_winding_moment* mom; u32 k; float m[12], c[9], smax; };
 
-__device__ __forceinline__ void wind_load_m(const SceneQuery& a, u32 k, float* m) {
-    const float4* mq = reinterpret_cast<const float4*>(reinterpret_cast<const bvh_instance*>(a.inst_in) + k);
-    const float4 m0 = mq[0], m1 = mq[1], m2 = mq[2];
-    m[0] = m0.x; m[1] = m0.y; m[2] = m0.z; m[3] = m0.w; m[4] = m1.x; m[5] = m1.y; m[6] = m1.z; m[7] = m1.w; m[8] = m2.x; m[9] = m2.y; m[10] = m2.z; m[11] = m2.w;
-}
 // instance k for a walk; false: out of range or inactive (it contributes nothing)
 __device__ __forceinline__ bool wind_enter(const SceneQuery& a, const SceneWind& sw, u32 k, WInst& I) {
     if (k >= a.n_inst) return false;
@@ -177,7 +164,7 @@ __device__ __forceinline__ bool wind_enter(const SceneQuery& a, const SceneWind&
     I.B = a.blas[bl];
     I.mom = sw.bmom + (sw.first[bl] - bl);
     I.k = k;
-    wind_load_m(a, k, I.m);
+    mat_rows(inst_load_m(a, k), I.m);
     const float4* cq = reinterpret_cast<const float4*>(sw.maps + k);
     const float4 c0 = cq[0], c1 = cq[1];
     const float2 c2 = *reinterpret_cast<const float2*>(cq + 2);

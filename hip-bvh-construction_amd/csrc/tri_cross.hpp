@@ -45,12 +45,6 @@ __device__ __forceinline__ bool tt_crosses(QF3 x1, QF3 x2, QF3 x3, QF3 y1, QF3 y
     return tt_edge(y1, y2, t1, t2, x1, x2, x3) || tt_edge(y2, y3, t2, t3, x1, x2, x3) || tt_edge(y3, y1, t3, t1, x1, x2, x3);
 }
 
-// triangle i of a mesh in the format named at run time (uniform over the launch)
-__device__ __forceinline__ void tt_query_fetch(int fmt, const TriSrc& s, u32 i, QF3& a, QF3& b, QF3& c) {
-    if (fmt == BVH_TRI_PADDED64) tri_fetch<BVH_TRI_PADDED64>(s, i, a, b, c);
-    else if (fmt == BVH_TRI_PACKED36) tri_fetch<BVH_TRI_PACKED36>(s, i, a, b, c);
-    else tri_fetch<BVH_TRI_INDEXED>(s, i, a, b, c);
-}
 __device__ __forceinline__ Box tt_box(QF3 a, QF3 b, QF3 c) { return stage_e_box(a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z); }
 
 } // namespace bvh
