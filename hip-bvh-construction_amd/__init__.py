@@ -43,7 +43,7 @@ KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4")])                         
 KNN_MAX_K = 32
 TRI_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("feature", "<u4"), ("reserved", "<u4")])                   # bvh_tri_hit (bvh_closest_tris)
 INSTANCE_KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4")])         # bvh_instance_knn_hit (bvh_scene_knn, bvh_scene_radius_search)
-INSTANCE_TRI_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("feature", "<u4"), ("instance", "<u4")])          # bvh_instance_tri_hit (bvh_scene_closest_tris)
+INSTANCE_TRI_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("feature", "<u4"), ("instance", "<u4")])          # bvh_instance_tri_hit (bvh_scene_closest_tris, bvh_scene_radius_tris)
 INSTANCE_PRIM = np.dtype([("prim", "<u4"), ("instance", "<u4")])                                                   # bvh_instance_prim (bvh_scene_overlap)
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
 TRANSFORMATION = np.dtype([("translation", "<f4", 3), ("pad", "<f4"), ("scale", "<f4", 3), ("pad1", "<f4"), ("quat", "<f4", 4), ("pad2", "<f4", 4)])
@@ -84,7 +84,7 @@ EXPORTS = [
     "bvh_ctx_set_option", "bvh_ctx_get_option", "bvh_abi_version", "bvh_abi_struct_sizes",
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
-    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap", "bvh_scene_intersect_tris", "bvh_scene_collide", "bvh_scene_closest_tris",
+    "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap", "bvh_scene_intersect_tris", "bvh_scene_collide", "bvh_scene_closest_tris", "bvh_scene_radius_tris",
     "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris", "bvh_closest_tris", "bvh_radius_tris",
     "bvh_scene_winding_prepare", "bvh_scene_winding_number", "bvh_scene_winding_moments", "bvh_scene_winding_instances",
@@ -133,6 +133,7 @@ RADIUS_TRIS_SORTED, RADIUS_TRIS_SELF, RADIUS_TRIS_SKIP_SHARED = 1, 2, 4   # BVH_
 SCENE_OVERLAP_SORTED = 1             # BVH_SCENE_OVERLAP_SORTED (bvh_scene_overlap's flag)
 SCENE_TRIS_QUERY, SCENE_TRIS_INSTANCE = 0, 1   # bvh_scene_tris_mode (bvh_scene_intersect_tris)
 SCENE_TRIS_SORTED = 1                # BVH_SCENE_TRIS_SORTED (bvh_scene_intersect_tris's flag)
+SCENE_RADIUS_TRIS_SORTED = 1         # BVH_SCENE_RADIUS_TRIS_SORTED (bvh_scene_radius_tris's flag)
 SCENE_COLLIDE_SORTED, SCENE_COLLIDE_BOTH = 1, 2   # bvh_scene_collide's flags
 SPLIT_MAX_DEPTH = 16                 # BVH_SPLIT_MAX_DEPTH (bvh_split_refs)
 ABI_VERSION = 4                      # BVH_ABI_VERSION of include/bvh_mi355x.h this binding was written against
@@ -250,6 +251,7 @@ def lib() -> C.CDLL:
         "bvh_scene_overlap": ([vp, vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_scene_intersect_tris": ([vp, C.POINTER(BuildInput), u32, i32, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_scene_closest_tris": ([vp, C.POINTER(BuildInput), u32, i32, u32, C.c_float, vp, i32], i32),
+        "bvh_scene_radius_tris": ([vp, C.POINTER(BuildInput), u32, i32, u32, C.c_float, u32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_scene_collide": ([vp, u32, vp, u32, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)], i32),
         "bvh_scene_winding_prepare": ([vp, u32], i32),
         "bvh_scene_winding_number": ([vp, vp, u32, C.c_float, vp], i32),
@@ -1767,6 +1769,38 @@ class Scene:
                 hits.free()
             if own is not None:
                 own.free()
+
+    def radius_tris(self, other=None, instance: int | None = None, radius=None, sorted: bool = True, count_only: bool = False,
+                    capacity: int | None = None, tri_format: int = TRI_PADDED64, vertices=None, indices=None, n_vertices: int = 0, n: int | None = None):
+        """bvh_scene_radius_tris: EVERY (instance, triangle) within ``radius`` (one bound for the call; None: +inf) of each query triangle, with its squared
+        world distance and feature pair.  The query side as for closest_tris: ``other``, a mesh in WORLD space (a host TRIANGLE array, a host (m, 9) or
+        (m, 3, 3) float array, a device buffer of records in ``tri_format`` with ``n``, or ``vertices`` / ``indices`` / ``n_vertices`` / ``n`` for a device
+        TRI_INDEXED mesh), or ``instance=k`` (BVH_SCENE_TRIS_INSTANCE): the rows are the world triangles of instance k's BLAS, instance k itself is skipped,
+        and the default ``n`` is the same upper bound (the largest n_leaves among the BLASes), rows at or beyond the instance's n_leaves empty.  Returns host
+        arrays (offsets u32[n + 1], records INSTANCE_TRI_HIT[total]): query i's records {dist2, prim, feature, instance} are
+        records[offsets[i]:offsets[i + 1]], in ascending (dist2, instance, prim) order when ``sorted`` (BVH_SCENE_RADIUS_TRIS_SORTED; quadratic in a slice's
+        length), in no particular order otherwise.  ``count_only`` returns offsets alone.  ``capacity`` None: a count-only call first, then a call with the
+        exact capacity; a given capacity that is too small is re-allocated with the total the call reported and the call repeated once."""
+        own, qin = None, None
+        if instance is not None:
+            if other is not None or vertices is not None or indices is not None:
+                raise BvhError("instance=k takes no other mesh")
+            mode, k = SCENE_TRIS_INSTANCE, int(instance)
+            if not 0 <= k < self.n_instances:
+                raise BvhError(f"instance {k} of a scene of {self.n_instances}")
+            n = int(n) if n is not None else getattr(self, "_max_leaves", 0)
+        else:
+            mode, k = SCENE_TRIS_QUERY, 0
+            other, tri_format, n, own = _as_mesh(self.ctx, other, tri_format, vertices, indices, n, "instance=k")
+        if n == 0:                                        # no queries: the empty answer, without a call
+            return _no_queries(count_only, INSTANCE_TRI_HIT)
+        if instance is None:
+            qin = _build_input(tri_format, other, vertices, indices, n_vertices)
+        r = float("inf") if radius is None else float(radius)
+        flags = SCENE_RADIUS_TRIS_SORTED if sorted else 0
+        self._sync_blas()
+        return _count_fill(self.ctx, lambda off, out, cap, tot: lib().bvh_scene_radius_tris(self.handle, _ref(qin), n, mode, k, r, flags, off, out, cap, tot), n,
+                           INSTANCE_TRI_HIT, count_only, capacity, "bvh_scene_radius_tris", own)
 
     def distance_to(self, other=None, instance: int | None = None, **mesh) -> float:
         """The distance between the scene and ``other`` (or, with ``instance=k``, between instance k and every other instance), query side and keyword

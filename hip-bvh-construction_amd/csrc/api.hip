@@ -539,7 +539,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_scene_closest_tris(); warm_scene_collide(); warm_scene_winding(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_closest_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_radius_tris(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_scene_closest_tris(); warm_scene_radius_tris(); warm_scene_collide(); warm_scene_winding(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_closest_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_radius_tris(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -1835,6 +1835,34 @@ int bvh_scene_closest_tris(bvh_scene* sc, const bvh_build_input* queries, uint32
     const SceneTris st{ TrisMesh{ (int)qin.tri_format, qin.d_tris, qin.d_vertices, qin.d_indices, qin.n_vertices }, mode, query_instance };
     return query_tail(sc->ctx, nullptr, sc->overflow, [&](hipStream_t s, u32* overflow) {
         launch_scene_closest_tris(s, query, radius, scene_query(sc, nullptr, n_queries, d_hits, overflow), st);
+    });
+}
+
+// bvh_radius_tris's query on a scene: bvh_scene_intersect_tris's validation block (in its order) with bvh_instance_tri_hit records, bvh_scene_radius_search's
+// tail; every argument is checked before anything is enqueued, so an error writes nothing
+int bvh_scene_radius_tris(bvh_scene* sc, const bvh_build_input* queries, uint32_t n_queries, int mode, uint32_t query_instance, float radius, uint32_t flags,
+                          uint32_t* d_offsets, bvh_instance_tri_hit* d_hits, uint64_t capacity, uint64_t* total_out) {
+    if (!sc || !d_offsets || !sc->built) return BVH_E_INVALID_ARG;
+    if (flags & ~BVH_SCENE_RADIUS_TRIS_SORTED) return BVH_E_INVALID_ARG;
+    if (mode != BVH_SCENE_TRIS_QUERY && mode != BVH_SCENE_TRIS_INSTANCE) return BVH_E_INVALID_ARG;
+    if ((mode == BVH_SCENE_TRIS_INSTANCE) != (queries == nullptr)) return BVH_E_INVALID_ARG;     // the world-space mesh, or none in instance mode
+    if (mode == BVH_SCENE_TRIS_INSTANCE ? query_instance >= sc->n_inst : query_instance != 0u) return BVH_E_INVALID_ARG;
+    if (n_queries >= (1u << 30)) return BVH_E_INVALID_ARG;
+    bvh_build_input qin;
+    std::memset(&qin, 0, sizeof qin);
+    if (queries) { if (stage_extents_valid(queries)) return BVH_E_INVALID_ARG; qin = *queries; }
+    {   // the output arrays against each other and against the query mesh
+        Range rs[4] = { Range(d_offsets, ((uint64_t)n_queries + 1u) * sizeof(u32)), fill_range(d_hits, capacity, sizeof(bvh_instance_tri_hit)) };
+        int k = 2;
+        if (queries) k += mesh_ranges(qin, n_queries, rs + k);
+        if (!disjoint(rs, 2, k)) return BVH_E_INVALID_ARG;
+    }
+    const SceneTris st{ TrisMesh{ (int)qin.tri_format, qin.d_tris, qin.d_vertices, qin.d_indices, qin.n_vertices }, mode, query_instance };
+    return count_fill_tail(sc->ctx, nullptr, n_queries, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
+        SceneQuery q = scene_query(sc, nullptr, n_queries, d_hits, overflow);
+        const SceneHits h{ d_offsets, d_hits, total, capacity };
+        launch_scene_radius_tris_count(s, radius, q, h, st, sc->ctx->overlap_sums, total);
+        if (d_hits) { q.overflow = overflow + 1; launch_scene_radius_tris_fill(s, (flags & BVH_SCENE_RADIUS_TRIS_SORTED) ? 1 : 0, radius, q, h, st); }
     });
 }
 

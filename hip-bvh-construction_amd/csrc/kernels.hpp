@@ -353,6 +353,12 @@ void launch_scene_tris_fill(hipStream_t s, int sorted, const SceneQuery& q, cons
 // one bound.  k_scene_closest_tris (short stack shared by both levels, marks a query it leaves in hits[i].prim_idx) + k_scene_closest_tris_deep (stackless,
 // returns at once while *q.overflow == 0)
 void launch_scene_closest_tris(hipStream_t s, int query, float radius, const SceneQuery& q, const SceneTris& t);
+// bvh_scene_radius_tris (scene_radius_tris.hip): launch_scene_tris_count's two calls with bvh_scene_closest_tris's candidates (q.rays is unused), with hits =
+// bvh_instance_tri_hit[capacity]; radius: the call's one bound.  k_scene_radius_tris_walk + k_scene_radius_tris_deep + launch_overlap_scan;
+// launch_scene_radius_tris_fill: the same two kernels' fill forms, which return at once unless *h.total <= h.capacity and *h.total < 2^32; query i's records
+// go to hits[offsets[i] ..], in ascending (dist2, instance, prim) order when sorted != 0
+void launch_scene_radius_tris_count(hipStream_t s, float radius, const SceneQuery& q, const SceneHits& h, const SceneTris& t, uint64_t* d_sums, uint64_t* d_total);
+void launch_scene_radius_tris_fill(hipStream_t s, int sorted, float radius, const SceneQuery& q, const SceneHits& h, const SceneTris& t);
 // bvh_scene_collide (scene_collide.hip): every instance's triangles ask at once (q.rays is unused, q.n_rays = row_capacity), with hits = bvh_instance_prim[capacity].
 // SceneCollide is the row table: d_row_first = the caller's u32[n_inst + 1], d_n_rows = a scratch u64 of its own (it must survive the count pass's scan, which
 // writes the query total elsewhere), both = BVH_SCENE_COLLIDE_BOTH.  launch_scene_collide_rows: k_scene_collide_rows (one thread per instance: n_leaves of its
@@ -407,6 +413,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_tris(); void warm_scene_closest_tris(); void warm_scene_collide(); void warm_scene_winding(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_closest_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_radius_tris(); void warm_split(); void warm_many(); void warm_many_ploc();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_tris(); void warm_scene_closest_tris(); void warm_scene_radius_tris(); void warm_scene_collide(); void warm_scene_winding(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_closest_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_radius_tris(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

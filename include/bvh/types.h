@@ -11,7 +11,8 @@
  *   bvh_tri_hit 16 B (bvh_closest_tris's output: the nearest tree triangle to a query triangle); no counterpart
  *   bvh_instance_knn_hit 16 B (one entry of bvh_scene_knn's lists and one record of bvh_scene_radius_search's slices: bvh_knn_hit with the instance, padded to one
  *     16-byte store); no counterpart
- *   bvh_instance_tri_hit 16 B (bvh_scene_closest_tris's output: bvh_tri_hit with the instance in its last word); no counterpart
+ *   bvh_instance_tri_hit 16 B (bvh_scene_closest_tris's output and one record of bvh_scene_radius_tris's slices: bvh_tri_hit with the instance in its last
+ *     word); no counterpart
  *   bvh_instance_prim 8 B (one record of bvh_scene_overlap's, bvh_scene_intersect_tris's and bvh_scene_collide's slices: a primitive of an instance); no counterpart
  * Usable from C, C++ and HIP device code. */
 #ifndef BVH_TYPES_H
@@ -61,7 +62,7 @@ typedef struct { bvh_float3 point; float dist2; float u, v; uint32_t prim_idx, i
  * instance_idx's triangle prim_idx; reserved = 0 (an unused slot of a k-nearest list: {radius*radius, BVH_INVALID, BVH_INVALID, 0}; a slice has no unused slots) */
 typedef struct { float dist2; uint32_t prim_idx, instance_idx, reserved; } bvh_instance_knn_hit;
 /* bvh_scene_closest_tris's answer to one query triangle: dist2 = the squared WORLD distance to triangle prim_idx of instance instance_idx, feature as in
- * bvh_tri_hit; a miss: {radius*radius, BVH_INVALID, 0, BVH_INVALID} */
+ * bvh_tri_hit; a miss: {radius*radius, BVH_INVALID, 0, BVH_INVALID}.  Also one record of bvh_scene_radius_tris's slices (a slice has no miss records) */
 typedef struct { float dist2; uint32_t prim_idx; uint32_t feature; uint32_t instance_idx; } bvh_instance_tri_hit;
 /* one record of bvh_scene_overlap's, bvh_scene_intersect_tris's and bvh_scene_collide's slices: triangle prim_idx of instance instance_idx (a slice has no unused slots) */
 typedef struct { uint32_t prim_idx, instance_idx; } bvh_instance_prim;

@@ -1148,6 +1148,57 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  *   asynchronous on the ctx's stream, no read-back, no depth limit at either level (queries whose short stack would overflow are finished by a stackless pass
  *     through the top-level plan and the BLAS plans, with the same boxes and candidates).  bvh_ctx_kernel_times reports k_scene_closest_tris and
  *     k_scene_closest_tris_deep.
+ * Every triangle within a radius, on scenes: bvh_scene_radius_tris is bvh_radius_tris on a scene — ALL triangles of all active instances within a distance
+ * of each query triangle, with the squared distance and the feature pair.  Contact generation between the rigid bodies of a scene: barrier and penalty
+ * methods want every vertex-face and edge-edge pair closer than a distance BEFORE the bodies touch (bvh_scene_intersect_tris and bvh_scene_collide are still
+ * empty then), after bvh_scene_update alone and without flattening the scene.  The contract is the union of bvh_scene_closest_tris's and bvh_radius_tris's;
+ * nothing in it is new arithmetic (tests/test_scene_radius_tris.py restates it in numpy).
+ *   query triangle i: bvh_scene_closest_tris's, word for word.  BVH_SCENE_TRIS_QUERY — triangle i of `queries`, n_queries triangles already in world space,
+ *     device pointers, any bvh_tri_format (morton_bits is ignored); query_instance must be 0.  BVH_SCENE_TRIS_INSTANCE — `queries` must be NULL and row i is
+ *     the world triangle (query_instance, i); the instance is looked up ON THE DEVICE (no read-back; it follows a bvh_scene_update from device memory); a row at
+ *     or beyond that BLAS's n_leaves is empty, every row of an inactive query instance is empty; the walk skips instance query_instance BY INDEX, a second
+ *     instance of the same BLAS is another instance and answers.  This mode reads triangle i of the BLAS's triangle array for every i < n_leaves and is NOT
+ *     usable on a BLAS over bvh_split_refs references relabelled by bvh_remap_leaves, which the call cannot check.
+ *   candidate of (i; k, j): bvh_closest_tris's dist2(X, Y) and feature, steps 0-4 word for word, with X = query triangle i and Y = the WORLD triangle (k, j):
+ *     V.r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3 with m_rc = object_to_world[4r + c], in f32 without contraction, in exactly this order.  The crossing test
+ *     (feature 15, dist2 0) runs only where the two world stage-E boxes overlap.  The value does not depend on how the scene is walked.
+ *   acceptance: r2 = radius * radius in f32, ONE bound for the whole call.  A candidate is accepted iff dist2 <= r2.  A NaN or negative radius, or a query
+ *     triangle with a NaN coordinate, makes the query dead: it accepts nothing.  Radius 0 accepts dist2 == 0, feature-15 crossings among them.  +inf accepts
+ *     every non-NaN candidate of every active instance.  Inactive instances never answer.
+ *   answer: ALL accepted candidates, in compressed-row form as bvh_scene_radius_search's: d_hits[d_offsets[i] .. d_offsets[i+1]) is query i's slice of
+ *     bvh_instance_tri_hit {dist2, prim_idx, feature, instance_idx} records, d_offsets[0] = 0, d_offsets[n_queries] = the total.  Each (instance, prim) pair
+ *     appears at most once per slice.  There are no miss records: an empty slice has nothing within the radius.  With d_hits == NULL the call only counts.
+ *   order inside a slice: without BVH_SCENE_RADIUS_TRIS_SORTED unspecified, but the same call on the same arrays gives the same bytes.  With it each slice is
+ *     ascending in (dist2, instance_idx, prim_idx), compared lexicographically; the arrays then depend on no builder, layout, format or traversal order, and
+ *     the first record of a non-empty slice is bvh_scene_closest_tris(BVH_QUERY_CLOSEST)'s record for the same radius, bit for bit.  The sorted insertion is
+ *     quadratic in the slice's length.
+ *   box tests: bvh_scene_closest_tris's at both levels, against r2 for the WHOLE walk — the bound never shrinks.  Top level: box_box_dist_pass on the
+ *     instances' world boxes (each grown by 2^-16 * its largest |coordinate|) against the query's world stage-E box grown once the same way.  Inside instance
+ *     k: the object box of the three mapped vertices x'_i = W_k x_i, grown on every axis by 2^-16 * (its largest |coordinate|) + e with e as there; a node box
+ *     grows by 2^-16 * (its largest |coordinate|); lb' = (gx*gx + gy*gy) + gz*gz over the per-axis gaps, and the subtree is culled iff
+ *     s2_k * lb' * (1 - 2^-20) > r2 (a NaN product never culls).  A leaf pair whose two WORLD stage-E boxes fail bvh_closest_tris's rule against r2 is skipped
+ *     before any term is computed.  Neither the top-level root's own box nor a BLAS root's own box is tested: the instance's world box stands for the BLAS root
+ *     (with n_instances == 1 the one world box is tested, then the instance entered).  This holds in both passes.
+ *   well-conditioned (the set exact): every accepted pair (i; k, j) meets bvh_scene_closest_tris's conditions (1) and (2) against its OWN dist2.  Then the
+ *     slice is the full set (8y's argument with a constant bound).  On every query each record is an accepted candidate of its (instance, prim)
+ *     with bit-equal dist2 and feature, and the slice is a subset of the true set.
+ *   relation to the other queries: with one identity instance, offsets and records equal bvh_radius_tris's on the BLAS byte for byte (its reserved 0 is
+ *     instance 0).  The feature-15 records at radius 0 are bvh_scene_intersect_tris's set.  Row i of INSTANCE(k) is NOT promised to mirror row j of
+ *     INSTANCE(l) bit for bit: dist2(X, Y) and dist2(Y, X) run their f32 terms in different roles.
+ *   passes, capacity, total_out, saturation, asynchrony, scratch words: exactly bvh_scene_radius_search's — the call always counts and scans; the fill decides
+ *     ON THE DEVICE whether it runs (d_hits != NULL, total <= capacity and total < 2^32); a skipped fill leaves d_hits untouched and d_offsets complete;
+ *     total_out != NULL is the only host wait; a total of 2^32 or more saturates d_offsets at 0xFFFFFFFF and returns BVH_E_TOO_LARGE when total_out was given
+ *     (with *total_out set); d_hits is never written outside query i's slice nor past the total; the per-query counter saturates at 0xFFFFFFFD; a
+ *     one-instance scene on a fresh ctx reserves the smallest arena at the first call.
+ *   no depth limit at either level: a query whose short stack would overflow is finished by a stackless pass through the plans the scene owns.  Both passes
+ *     test the same boxes and the same candidates, so count and fill agree on every query's set whichever pass served it.
+ *   errors enqueue and write nothing (BVH_E_INVALID_ARG), bvh_scene_intersect_tris's in its order: a NULL or unbuilt scene; NULL d_offsets; a flag bit other
+ *     than BVH_SCENE_RADIUS_TRIS_SORTED; mode not 0 or 1; NULL queries with BVH_SCENE_TRIS_QUERY; queries given with BVH_SCENE_TRIS_INSTANCE;
+ *     query_instance >= n_instances with BVH_SCENE_TRIS_INSTANCE, query_instance != 0 with BVH_SCENE_TRIS_QUERY; n_queries >= 2^30; a format error in queries
+ *     (as for bvh_scene_intersect_tris); d_offsets or d_hits (capacity records, clamped to 2^32 - 1) overlapping each other or the query mesh's triangle,
+ *     vertex or index array.
+ *   n_queries == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
+ *   bvh_ctx_kernel_times reports k_scene_radius_tris_walk (count and fill), k_scene_radius_tris_deep (after each pass) and k_overlap_scan.
  * Winding numbers: bvh_scene_winding_number is bvh_winding_number on a scene — inside / outside against an assembly of bodies, the sign for
  * bvh_scene_closest_point's distance, voxelisation and point-in-union over thousands of bvh_build_many bodies — without flattening the scene.  Two calls:
  * bvh_scene_winding_prepare after a build or an update, bvh_scene_winding_number per batch of points (tests/test_scene_winding.py restates both in numpy).
@@ -1233,6 +1284,12 @@ int  bvh_scene_collide(bvh_scene* scene, uint32_t flags /* BVH_SCENE_COLLIDE_SOR
 int  bvh_scene_closest_tris(bvh_scene* scene, const bvh_build_input* queries /* world-space mesh, device, any bvh_tri_format; NULL with BVH_SCENE_TRIS_INSTANCE */,
                             uint32_t n_queries, int mode /* bvh_scene_tris_mode */, uint32_t query_instance /* BVH_SCENE_TRIS_INSTANCE only, else 0 */,
                             float radius, bvh_instance_tri_hit* d_hits /* [n_queries], device */, int query /* bvh_query_kind */);
+#define BVH_SCENE_RADIUS_TRIS_SORTED 1u
+int  bvh_scene_radius_tris(bvh_scene* scene, const bvh_build_input* queries /* world-space mesh, device, any bvh_tri_format; NULL with BVH_SCENE_TRIS_INSTANCE */,
+                           uint32_t n_queries, int mode /* bvh_scene_tris_mode */, uint32_t query_instance /* BVH_SCENE_TRIS_INSTANCE only, else 0 */,
+                           float radius, uint32_t flags /* 0 or BVH_SCENE_RADIUS_TRIS_SORTED */, uint32_t* d_offsets /* u32[n_queries + 1], device */,
+                           bvh_instance_tri_hit* d_hits /* [capacity], device, or NULL: count only */, uint64_t capacity,
+                           uint64_t* total_out /* host, may be NULL */);
 #define BVH_SCENE_WINDING_KEEP_BLAS 1u
 int  bvh_scene_winding_prepare(bvh_scene* scene, uint32_t flags /* 0 or BVH_SCENE_WINDING_KEEP_BLAS */);
 int  bvh_scene_winding_number(bvh_scene* scene, const bvh_point_query* d_points /* radius ignored */, uint32_t n_points, float beta,
