@@ -45,6 +45,11 @@ TRI_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("feature", "<u4"), ("res
 INSTANCE_KNN_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("instance", "<u4"), ("reserved", "<u4")])         # bvh_instance_knn_hit (bvh_scene_knn, bvh_scene_radius_search)
 INSTANCE_TRI_HIT = np.dtype([("dist2", "<f4"), ("prim", "<u4"), ("feature", "<u4"), ("instance", "<u4")])          # bvh_instance_tri_hit (bvh_scene_closest_tris, bvh_scene_radius_tris)
 INSTANCE_PRIM = np.dtype([("prim", "<u4"), ("instance", "<u4")])                                                   # bvh_instance_prim (bvh_scene_overlap)
+CULL_HIT = np.dtype([("prim", "<u4"), ("straddle", "<u4")])                                                        # bvh_cull_hit (bvh_cull)
+CULL_AUTO, CULL_LANE, CULL_GROUP = 0, 1, 2   # bvh_cull_path
+CULL_PATHS = {"auto": CULL_AUTO, "lane": CULL_LANE, "group": CULL_GROUP}
+CULL_MAX_PLANES = 8                          # BVH_CULL_MAX_PLANES
+CULL_GROUP_STACK = 8192                      # BVH_CULL_GROUP_STACK
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
 TRANSFORMATION = np.dtype([("translation", "<f4", 3), ("pad", "<f4"), ("scale", "<f4", 3), ("pad1", "<f4"), ("quat", "<f4", 4), ("pad2", "<f4", 4)])
 assert RAY.itemsize == 32 and CAMERA.itemsize == 64 and TRANSFORMATION.itemsize == 64 and INSTANCE.itemsize == 64 and INSTANCE_HIT.itemsize == 32
@@ -85,7 +90,7 @@ EXPORTS = [
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap", "bvh_scene_intersect_tris", "bvh_scene_collide", "bvh_scene_closest_tris", "bvh_scene_radius_tris",
-    "bvh_closest_point", "bvh_overlap", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
+    "bvh_closest_point", "bvh_overlap", "bvh_cull", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris", "bvh_closest_tris", "bvh_radius_tris",
     "bvh_scene_winding_prepare", "bvh_scene_winding_number", "bvh_scene_winding_moments", "bvh_scene_winding_instances",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
@@ -260,6 +265,7 @@ def lib() -> C.CDLL:
         "bvh_closest_point": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, vp, i32], i32),
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_cull": ([vp, C.POINTER(Result), vp, u32, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_intersect_tris": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(BuildInput), u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_closest_tris": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(BuildInput), u32, C.c_float, vp, i32], i32),
         "bvh_intersect_all": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
@@ -469,6 +475,95 @@ def _no_queries(count_only, rec_dtype):
     """the answer to no queries, given without a call"""
     off = np.zeros(1, dtype=np.uint32)
     return off if count_only else (off, np.zeros(0, dtype=rec_dtype))
+
+
+def frustum_planes(m, depth_zero_to_one: bool = True) -> np.ndarray:
+    """The six Gribb-Hartmann planes of a row-major 4x4 clip matrix in the column-vector convention (clip = m @ [x, y, z, 1]): left, right, bottom, top, near,
+    far as an f32 (6, 4) array of (a, b, c, d), not normalised, inside-positive (a x + b y + c z + d >= 0), as bvh_cull takes them.  The depth pair follows
+    0 <= z <= w (``depth_zero_to_one``) or -w <= z <= w."""
+    m = np.asarray(m, dtype=np.float32).reshape(4, 4)
+    r0, r1, r2, r3 = m
+    return np.stack([r3 + r0, r3 - r0, r3 + r1, r3 - r1, r2 if depth_zero_to_one else r3 + r2, r3 - r2]).astype(np.float32)
+
+
+def _box_corners(leaf_boxes):
+    """(lo, hi), each f32 (n, 3), of AABB records or an (n, 6) float array (min xyz, max xyz)"""
+    b = np.asarray(leaf_boxes)
+    if b.dtype == AABB:
+        return np.ascontiguousarray(b["min"], dtype=np.float32), np.ascontiguousarray(b["max"], dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 6)
+    return b[:, :3], b[:, 3:]
+
+
+def cull_plane_values(planes, lo, hi):
+    """bvh_cull's plane test in numpy f32, every product and every sum a separate np.float32 operation: planes (..., 4) against boxes lo / hi (..., 3), shapes
+    broadcast.  Returns (s_p, s_n): s at the p-vertex (p.k = hi.k where n.k >= 0, else lo.k) and at the n-vertex (the other choice)."""
+    pl = np.asarray(planes, dtype=np.float32); lo = np.asarray(lo, dtype=np.float32); hi = np.asarray(hi, dtype=np.float32)
+    d = pl[..., 3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        sel = [pl[..., k] >= np.float32(0.0) for k in range(3)]
+
+        def s_of(v):
+            x = pl[..., 0] * v[0]; y = pl[..., 1] * v[1]; z = pl[..., 2] * v[2]
+            t = x + y
+            t = t + z
+            return (t + d).astype(np.float32)
+        s_p = s_of([np.where(sel[k], hi[..., k], lo[..., k]) for k in range(3)])
+        s_n = s_of([np.where(sel[k], lo[..., k], hi[..., k]) for k in range(3)])
+    return s_p, s_n
+
+
+def cull_brute_force(planes, leaf_boxes):
+    """bvh_cull's defined answer by testing every leaf box against every volume (the reference of the CPU and of the GPU tests).  ``planes``: floats
+    (n_volumes, planes_per_volume, 4), or (planes_per_volume, 4) for one volume; ``leaf_boxes``: AABB records or (n, 6) floats, indexed by primitive.  A box
+    passes a volume iff it is valid (min <= max on every axis, a NaN fails) and s(p-vertex) >= 0 for every plane; bit k of its straddle mask is
+    !(s(n-vertex of plane k) >= 0).  Returns (offsets u32[n_volumes + 1], hits CULL_HIT[total]), every slice in ascending prim order."""
+    pl = np.asarray(planes, dtype=np.float32)
+    if pl.ndim == 2:
+        pl = pl[None]
+    if pl.ndim != 3 or pl.shape[2] != 4 or not 1 <= pl.shape[1] <= CULL_MAX_PLANES:
+        raise BvhError("planes must have shape (n_volumes, 1..8, 4) or (1..8, 4)")
+    lo, hi = _box_corners(leaf_boxes)
+    with np.errstate(invalid="ignore"):
+        valid = (lo <= hi).all(axis=1)
+    bits = (np.uint32(1) << np.arange(pl.shape[1], dtype=np.uint32))[:, None]
+    counts, rows = np.zeros(len(pl) + 1, dtype=np.uint64), []
+    for i, vol in enumerate(pl):
+        s_p, s_n = cull_plane_values(vol[:, None, :], lo[None], hi[None])             # (planes, n)
+        with np.errstate(invalid="ignore"):
+            inside = valid & (s_p >= np.float32(0.0)).all(axis=0)
+            mask = np.where(s_n >= np.float32(0.0), np.uint32(0), bits).sum(axis=0, dtype=np.uint32)
+        prims = np.nonzero(inside)[0]
+        rec = np.zeros(len(prims), dtype=CULL_HIT)
+        rec["prim"] = prims; rec["straddle"] = mask[prims]
+        rows.append(rec); counts[i + 1] = len(prims)
+    offsets = np.minimum(np.cumsum(counts), 0xFFFFFFFF).astype(np.uint32)
+    return offsets, (np.concatenate(rows) if rows else np.zeros(0, dtype=CULL_HIT))
+
+
+def cull(ctx, result, planes, path="auto", count_only: bool = False, capacity: int | None = None):
+    """bvh_cull on any tree bvh_overlap accepts (``result``: a builder's result, a bvh_build_boxes tree, Scene.tlas(), caller-filled arrays): which primitives'
+    leaf boxes pass each convex volume.  ``planes``: host floats (n_volumes, planes_per_volume, 4) — or (planes_per_volume, 4) for one volume —, each plane
+    (a, b, c, d) with its inside a x + b y + c z + d >= 0, 1 to 8 planes per volume (frustum_planes gives a camera's six).  ``path``: "auto", "lane" (one volume
+    per lane) or "group" (one volume per workgroup), or a bvh_cull_path value.  Returns host arrays (offsets u32[n_volumes + 1], hits CULL_HIT[total]): volume
+    i's records are hits[offsets[i]:offsets[i + 1]], in no particular order; ``straddle == 0`` marks a box wholly inside the volume.  ``count_only`` returns
+    offsets alone.  ``capacity`` None: a count-only call first, then a call with the exact capacity; a given capacity that is too small is re-allocated with
+    the total the call reported and the call repeated once."""
+    pl = np.ascontiguousarray(planes, dtype=np.float32)
+    if pl.ndim == 2:
+        pl = pl[None]
+    if pl.ndim != 3 or pl.shape[2] != 4 or not 1 <= pl.shape[1] <= CULL_MAX_PLANES:
+        raise BvhError("planes must have shape (n_volumes, 1..8, 4) or (1..8, 4)")
+    if path not in CULL_PATHS and path not in CULL_PATHS.values():
+        raise BvhError('path must be "auto", "lane" or "group"')
+    mode = CULL_PATHS.get(path, path)
+    n, per = pl.shape[0], pl.shape[1]
+    if n == 0:                                            # no volumes: the empty answer, without a call
+        return _no_queries(count_only, CULL_HIT)
+    own = ctx.upload(pl)
+    res = C.byref(result)
+    return _count_fill(ctx, lambda off, out, cap, tot: lib().bvh_cull(ctx.handle, res, own.ptr, n, per, mode, off, out, cap, tot), n, CULL_HIT, count_only,
+                       capacity, "bvh_cull", own)
 
 
 def many_layout(counts):
@@ -1213,6 +1308,11 @@ class _Builder:
         res = C.byref(self.result)
         return _count_fill(ctx, lambda off, out, cap, tot: lib().bvh_overlap(ctx.handle, res, _ptr(boxes), n, mode, off, out, cap, tot), n, np.uint32, False,
                            max(int(capacity) if capacity is not None else 8 * n, 1), f"{ALGO_NAMES[self.ALGO]}::overlap", own)
+    def cull(self, planes, path="auto", count_only: bool = False, capacity: int | None = None):
+        """bvh_cull on this builder's tree: which primitives' leaf boxes pass each convex volume of ``planes`` (see the module's cull)."""
+        if self._ctx is None:
+            raise BvhError("cull needs a built tree")
+        return cull(self._ctx, self.result, planes, path, count_only, capacity)
     def intersect_tris(self, other=None, self_pairs: bool = False, capacity: int | None = None, tri_format: int = TRI_PADDED64, vertices=None, indices=None,
                        n_vertices: int = 0, n: int | None = None, tree_tris=None, tree_vertices=None, tree_indices=None, tree_n_vertices: int = 0,
                        tree_tri_format: int = TRI_PADDED64):
@@ -1905,6 +2005,11 @@ class Scene:
         with np.errstate(invalid="ignore"):
             d = np.sqrt(hits["dist2"])
             return np.where(w > np.float32(0.5), -d, d).astype(np.float32), hits
+
+    def cull_instances(self, planes, path="auto", count_only: bool = False, capacity: int | None = None):
+        """bvh_cull on this scene's top-level tree (tlas()): which instances' world boxes pass each convex volume of ``planes``; the records' ``prim`` is the
+        instance index (see the module's cull)."""
+        return cull(self.ctx, self.tlas(), planes, path, count_only, capacity)
 
     def tlas(self) -> Result:
         r = Result()

@@ -1113,6 +1113,31 @@ int bvh_overlap(bvh_ctx* c, const bvh_result* tree, const bvh_aabb* d_boxes, uin
     });
 }
 
+// ---- convex-volume queries (no counterpart in the reference) ---------------------------------------------------------------------------------------
+// bvh_overlap's checks and tail, with planes in place of boxes; every argument is checked before anything is enqueued, so an error writes nothing.  The walk is
+// chosen here: BVH_CULL_AUTO takes the group walk for few volumes on a tree large enough to fill a workgroup's rounds (kernels.hpp's two constants)
+int bvh_cull(bvh_ctx* c, const bvh_result* tree, const float* d_planes, uint32_t n_volumes, uint32_t planes_per_volume, int path, uint32_t* d_offsets,
+             bvh_cull_hit* d_hits, uint64_t capacity, uint64_t* total_out) {
+    if (!c || !tree || !d_planes || !d_offsets) return BVH_E_INVALID_ARG;
+    if (!tree_valid(tree)) return BVH_E_INVALID_ARG;
+    const uint32_t n = tree->n_leaves;
+    if (planes_per_volume < 1u || planes_per_volume > (uint32_t)BVH_CULL_MAX_PLANES) return BVH_E_INVALID_ARG;
+    if (path != BVH_CULL_AUTO && path != BVH_CULL_LANE && path != BVH_CULL_GROUP) return BVH_E_INVALID_ARG;
+    if (n_volumes >= (1u << 30)) return BVH_E_INVALID_ARG;
+    if (n > c->cap) return BVH_E_INVALID_ARG;                 // (the parent plan lives in the arena's parent array: bvh_ctx_reserve first)
+    const Range rs[3] = { Range(d_planes, (uint64_t)n_volumes * planes_per_volume * 4u * sizeof(float)), Range(d_offsets, ((uint64_t)n_volumes + 1u) * sizeof(u32)),
+                          fill_range(d_hits, capacity, sizeof(bvh_cull_hit)) };
+    if (!disjoint(rs, 3, 3)) return BVH_E_INVALID_ARG;        // the three caller arrays must not overlap
+    const bool group = path == BVH_CULL_GROUP || (path == BVH_CULL_AUTO && n_volumes <= CULL_AUTO_MAX_VOLUMES && n >= CULL_AUTO_MIN_LEAVES);
+    return count_fill_tail(c, tree, n_volumes, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
+        launch_cull_count(s, (int)tree->layout, group, d_planes, n_volumes, planes_per_volume, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, overflow,
+                          c->parent, c->overlap_sums, total);
+        if (d_hits)
+            launch_cull_fill(s, (int)tree->layout, group, d_planes, n_volumes, planes_per_volume, tree->d_nodes, tree->d_leaves, n, tree->root, d_offsets, d_hits,
+                             capacity, total, overflow + 1, c->parent);
+    });
+}
+
 // ---- crossing triangle pairs (no counterpart in the reference) -------------------------------------------------------------------------------------
 // bvh_overlap's tail, with the query mesh's triangles in place of boxes; every argument is checked before anything is enqueued, so an error writes nothing.
 // Neither output array may overlap the other or any array the call reads

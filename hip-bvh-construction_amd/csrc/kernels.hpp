@@ -214,6 +214,21 @@ void launch_overlap_fill(hipStream_t s, int layout, int mode, const void* d_boxe
 // the scan alone (launch_overlap_count ends with it): d_offsets' n_boxes counts become n_boxes + 1 offsets in place, *d_total the 64-bit total
 void launch_overlap_scan(hipStream_t s, uint32_t* d_offsets, uint32_t n_boxes, uint64_t* d_sums, uint64_t* d_total);
 
+// ---- convex-volume queries (cull.hip): bvh_cull's kernels.  d_planes: float[n_volumes][planes][4].  group false: k_cull_walk (one volume per lane, short stack);
+// group true: k_cull_group (one volume per workgroup of CULL_GROUP_BLOCK threads, LDS work stack of BVH_CULL_GROUP_STACK entries).  Either marks a volume it
+// cannot finish and k_cull_deep (stackless, returns at once while *d_overflow == 0) redoes it.  launch_cull_count ends with launch_overlap_scan;
+// launch_cull_fill's kernels return at once unless *d_total <= capacity and *d_total < 2^32; volume i's bvh_cull_hit records go to d_hits[d_offsets[i] ..].
+// Each pass has an overflow word of its own, zeroed before the launches
+constexpr int CULL_GROUP_BLOCK = 256;
+constexpr uint32_t CULL_AUTO_MAX_VOLUMES = 65536;            // BVH_CULL_AUTO takes the group walk iff n_volumes <= this (the largest count measured: the group walk won there) ...
+constexpr uint32_t CULL_AUTO_MIN_LEAVES = 1024;              // ... and n_leaves >= this
+void launch_cull_count(hipStream_t s, int layout, bool group, const float* d_planes, uint32_t n_volumes, uint32_t planes, const void* d_nodes,
+                       const void* d_leaves, uint32_t n, uint32_t root, uint32_t* d_offsets, uint32_t* d_overflow, const uint32_t* d_parent, uint64_t* d_sums,
+                       uint64_t* d_total);
+void launch_cull_fill(hipStream_t s, int layout, bool group, const float* d_planes, uint32_t n_volumes, uint32_t planes, const void* d_nodes,
+                      const void* d_leaves, uint32_t n, uint32_t root, uint32_t* d_offsets, void* d_hits, uint64_t capacity, const uint64_t* d_total,
+                      uint32_t* d_overflow, const uint32_t* d_parent);
+
 // ---- crossing triangle pairs (intersect_tris.hip): bvh_intersect_tris' kernels.  A TrisMesh is one triangle array in a bvh_tri_format (device pointers);
 // tree_tris: the tree's triangles, queries: the other mesh's (self mode: the same array).  launch_tris_count: k_tris_count (short stack; d_offsets[i] = the number
 // of tree triangles query triangle i crosses) + k_tris_deep (stackless, returns at once while *d_overflow == 0) + launch_overlap_scan.  launch_tris_fill:

@@ -543,6 +543,58 @@ int  bvh_overlap(bvh_ctx* ctx, const bvh_result* tree, const bvh_aabb* d_boxes, 
                  uint32_t* d_offsets /* u32[n_boxes + 1], device */, uint32_t* d_prims /* u32[capacity], device, or NULL: count only */,
                  uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
 
+/* ---- convex-volume and frustum queries (no counterpart in the reference) ---------------------------------------------------------------
+ * Which primitives lie inside or across each convex volume?  View-frustum culling, the tile and cluster volumes of a light-culling pass, shadow cascades,
+ * "which instances are in view" on a scene's top-level tree.  bvh_overlap with a frustum's bounding box answers a superset that the caller must filter; this
+ * call takes the planes themselves.
+ * tree: anything bvh_overlap accepts, read as it is — a build's, a refit's, an optimised one, a bvh_build_boxes tree, a bvh_scene_tlas result (the answers are
+ * then instance indices), or caller-filled device arrays.  Only root, n_leaves, layout, d_nodes and d_leaves are read; no triangles are needed; nothing in the
+ * tree is written.  A primitive's box is its leaf record's box, as in bvh_overlap.
+ * Planes and volumes: d_planes[i][k] = (a, b, c, d) is plane k of volume i; its inside is a x + b y + c z + d >= 0; it need not be normalised.  A volume is the
+ * intersection of its planes_per_volume (1 .. BVH_CULL_MAX_PLANES) half-spaces; a caller with fewer real planes pads with (0, 0, 0, 1).
+ * The test, for a plane with n = (a, b, c) and a box [lo, hi] with lo.k <= hi.k on every axis (bvh_overlap's validity test), in IEEE f32:
+ *   p-vertex: p.k = (n.k >= 0) ? hi.k : lo.k (so -0.0 selects hi); the n-vertex takes the other choice on every axis;
+ *   s(v) = fadd(fadd(fadd(fmul(a, v.x), fmul(b, v.y)), fmul(c, v.z)), d), every product and sum ONE round-to-nearest f32 operation (never an FMA);
+ *   the box passes the plane iff s(p) >= 0 — a NaN fails —, and passes the volume iff it passes every plane;
+ *   bit k of straddle = !(s(n-vertex of plane k) >= 0): the box is not wholly inside plane k.  straddle == 0: the box lies wholly inside the volume (a
+ *   renderer then skips clipping).  An invalid box (inverted, or with a NaN) passes nothing.
+ * This is the standard conservative box test: a box beyond a corner or an edge of the volume can pass every plane without touching the volume.  That is the
+ * defined answer, not an error.
+ * Answer: volume i's slice d_hits[d_offsets[i] .. d_offsets[i+1]) holds one record per primitive whose leaf box passes volume i, with that leaf box's straddle
+ * mask (always worked out from the leaf's own box against all planes); compressed rows as bvh_overlap's, d_offsets[0] = 0, d_offsets[n_volumes] = the total.
+ * Each primitive appears at most once per slice.  The order inside a slice is unspecified, but the same call on the same arrays with the same path gives the
+ * same bytes.
+ * Exactness condition: every internal box contains its children's boxes — true bitwise of every tree this library makes —, and no evaluation of s produces a
+ * NaN — true of finite boxes and planes whose products and sums do not overflow.  The test is monotone under containment in rounded f32 (products by a fixed
+ * factor and sums are monotone, and the p-vertex takes the larger coordinate of every product), so every box above a passing leaf passes: the set is exact for
+ * EVERY volume and does not depend on the builder, the layout or the path.  Outside that condition every reported primitive still passes its own leaf test,
+ * but some may be left out.  A walk may drop plane k below a node whose n-vertex has s >= 0 (s(n_parent) <= s(n_child) <= s(p_child)): result-preserving under
+ * the same condition.  Arrays that are not a tree end in finite time with unspecified answers (d_hits is never written outside volume i's slice); a child or
+ * primitive index out of range is never followed or reported.
+ * path: BVH_CULL_LANE walks one volume per lane (thousands of small volumes); BVH_CULL_GROUP gives each volume a workgroup of 256 threads and a work stack of
+ * BVH_CULL_GROUP_STACK node indices in LDS (one camera frustum on a large tree); BVH_CULL_AUTO takes the group walk iff n_volumes <= 65536 and n_leaves >= 1024.
+ * The group walk's schedule is fixed: each round takes the m = min(top, 256) entries at the top of the stack, thread t entry top - m + t, tests both children,
+ * and emits leaf survivors / pushes internal survivors in thread order, left child before right — so its slice bytes are deterministic too.
+ * Passes, capacity, total_out, saturation and BVH_E_TOO_LARGE: bvh_overlap's, word for word.  The call always counts, then scans the counts into d_offsets, and
+ * fills d_hits iff d_hits != NULL, total <= capacity and total < 2^32, decided ON THE DEVICE; if the fill is skipped d_hits is not touched and d_offsets is
+ * still complete.  With total_out != NULL the call blocks on an 8-byte read-back.
+ * There is no depth or size limit: a volume whose short stack (lane walk) or work stack (group walk) would overflow is finished by a stackless pass through
+ * bvh_refit's parent plan, as in bvh_overlap.  Count and fill agree on every volume's set whichever walk served it.
+ * Errors (nothing is written or enqueued, BVH_E_INVALID_ARG): NULL ctx / tree / d_planes / d_offsets, the tree errors of bvh_overlap, planes_per_volume
+ * outside 1 .. 8, path outside 0 .. 2, n_volumes >= 2^30, n_leaves larger than the ctx's capacity (bvh_ctx_reserve first), d_offsets or d_hits (capacity
+ * records) overlapping d_planes or each other.
+ * n_volumes == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.
+ * bvh_ctx_kernel_times reports k_cull_walk or k_cull_group (count and fill), k_cull_deep (after each pass), k_overlap_scan (the scan is bvh_overlap's) and,
+ * when the plan is made, k_refit_plan. */
+typedef struct { uint32_t prim; uint32_t straddle; } bvh_cull_hit;          /* 8 bytes */
+typedef enum { BVH_CULL_AUTO = 0, BVH_CULL_LANE = 1, BVH_CULL_GROUP = 2 } bvh_cull_path;
+#define BVH_CULL_MAX_PLANES   8
+#define BVH_CULL_GROUP_STACK  8192       /* entries of the group walk's LDS work stack (32 KiB: four workgroups still fit a CU's 160 KiB) */
+int  bvh_cull(bvh_ctx* ctx, const bvh_result* tree, const float* d_planes /* float[n_volumes][planes_per_volume][4], device */,
+              uint32_t n_volumes, uint32_t planes_per_volume /* 1 .. 8 */, int path /* bvh_cull_path */,
+              uint32_t* d_offsets /* u32[n_volumes + 1], device */, bvh_cull_hit* d_hits /* [capacity], device, or NULL: count only */,
+              uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+
 /* ---- crossing triangle pairs (no counterpart in the reference) ---------------------------------------------------------------------------
  * Which triangles of the tree does each triangle of another mesh cut — or, with BVH_TRIS_SELF, which triangles of the tree's own mesh cut each other?  Contact
  * detection, self-intersection checks before meshing or booleans, mesh validation before a winding-number field.  bvh_overlap's broad phase and the exact narrow
