@@ -50,6 +50,8 @@ CULL_AUTO, CULL_LANE, CULL_GROUP = 0, 1, 2   # bvh_cull_path
 CULL_PATHS = {"auto": CULL_AUTO, "lane": CULL_LANE, "group": CULL_GROUP}
 CULL_MAX_PLANES = 8                          # BVH_CULL_MAX_PLANES
 CULL_GROUP_STACK = 8192                      # BVH_CULL_GROUP_STACK
+SCENE_CULL_HIT = np.dtype([("prim", "<u4"), ("instance", "<u4"), ("straddle", "<u4"), ("zero", "<u4")])                # bvh_scene_cull_hit (bvh_scene_cull)
+SCENE_CULL_GROUP_STACK = 8192                # BVH_SCENE_CULL_GROUP_STACK
 CAMERA = np.dtype([("eye", "<f4", 4), ("quat", "<f4", 4), ("fov", "<f4"), ("near", "<f4"), ("far", "<f4"), ("pad", "<f4"), ("pad2", "<f4", 4)])
 TRANSFORMATION = np.dtype([("translation", "<f4", 3), ("pad", "<f4"), ("scale", "<f4", 3), ("pad1", "<f4"), ("quat", "<f4", 4), ("pad2", "<f4", 4)])
 assert RAY.itemsize == 32 and CAMERA.itemsize == 64 and TRANSFORMATION.itemsize == 64 and INSTANCE.itemsize == 64 and INSTANCE_HIT.itemsize == 32
@@ -82,7 +84,7 @@ ALGO_NAMES = {0: "TwoPassLbvh", 1: "SinglePassLbvh", 2: "PLOCNew", 3: "HPLOC"}
 # every symbol include/bvh_mi355x.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "bvh_ctx_create", "bvh_ctx_create_on_stream", "bvh_ctx_destroy", "bvh_ctx_reserve", "bvh_ctx_device", "bvh_ctx_stream",
-    "bvh_ctx_set_profiling", "bvh_ctx_kernel_times", "bvh_ctx_synchronize", "bvh_build", "bvh_build_ex", "bvh_stage_extents", "bvh_stage_extents_ex",
+    "bvh_ctx_set_profiling", "bvh_ctx_kernel_times", "bvh_ctx_synchronize", "bvh_ctx_query_overflow", "bvh_build", "bvh_build_ex", "bvh_stage_extents", "bvh_stage_extents_ex",
     "bvh_stage_morton", "bvh_stage_morton64", "bvh_stage_morton_plan", "bvh_sort_pairs", "bvh_sort_pairs64",
     "bvh_emit_lbvh_single", "bvh_emit_lbvh_two", "bvh_emit_ploc", "bvh_emit_hploc", "bvh_to_lbvh_layout", "bvh_collapse4", "bvh_generate_rays", "bvh_trace_while", "bvh_trace", "bvh_sah_cost",
     "bvh_ctx_set_kernel_filter", "bvh_ctx_set_kernel_sampling", "bvh_bvh4_cost", "bvh_checksum", "bvh_ctx_last_collapse_ms", "bvh_batch_create", "bvh_batch_build", "bvh_batch_download", "bvh_batch_destroy",
@@ -90,7 +92,7 @@ EXPORTS = [
     "bvh_download", "bvh_dev_alloc", "bvh_dev_free", "bvh_dev_upload", "bvh_dev_download", "bvh_dev_copy", "bvh_batched_build", "bvh_version",
     "bvh_refit", "bvh_refit_ex", "bvh_intersect", "bvh_optimize",
     "bvh_build_boxes", "bvh_scene_create", "bvh_scene_destroy", "bvh_scene_build", "bvh_scene_update", "bvh_scene_intersect", "bvh_scene_tlas", "bvh_scene_closest_point", "bvh_scene_intersect_all", "bvh_scene_knn", "bvh_scene_radius_search", "bvh_scene_overlap", "bvh_scene_intersect_tris", "bvh_scene_collide", "bvh_scene_closest_tris", "bvh_scene_radius_tris",
-    "bvh_closest_point", "bvh_overlap", "bvh_cull", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
+    "bvh_closest_point", "bvh_overlap", "bvh_cull", "bvh_scene_cull", "bvh_knn", "bvh_intersect_all", "bvh_refit_subset", "bvh_radius_search",
     "bvh_winding_prepare", "bvh_winding_number", "bvh_intersect_tris", "bvh_closest_tris", "bvh_radius_tris",
     "bvh_scene_winding_prepare", "bvh_scene_winding_number", "bvh_scene_winding_moments", "bvh_scene_winding_instances",
     "bvh_split_refs", "bvh_remap_leaves", "bvh_build_many", "bvh_many_tree", "bvh_build_many_ploc", "bvh_many_ploc_tree",
@@ -204,6 +206,7 @@ def lib() -> C.CDLL:
         "bvh_ctx_create": ([i32, C.POINTER(vp)], i32), "bvh_ctx_create_on_stream": ([i32, vp, C.POINTER(vp)], i32),
         "bvh_ctx_destroy": ([vp], None), "bvh_ctx_reserve": ([vp, u32], i32), "bvh_ctx_device": ([vp], i32),
         "bvh_ctx_stream": ([vp], vp), "bvh_ctx_set_profiling": ([vp, i32], i32), "bvh_ctx_synchronize": ([vp], i32),
+        "bvh_ctx_query_overflow": ([vp, C.POINTER(u32), C.POINTER(u32)], i32),
         "bvh_build": ([vp, i32, vp, u32, i32, C.POINTER(Result), C.POINTER(Timings)], i32),
         "bvh_build_ex": ([vp, i32, C.POINTER(BuildInput), u32, C.POINTER(Result), C.POINTER(Timings)], i32),
         "bvh_stage_extents_ex": ([vp, C.POINTER(BuildInput), u32, vp, vp], i32),
@@ -266,6 +269,7 @@ def lib() -> C.CDLL:
         "bvh_knn": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp], i32),
         "bvh_overlap": ([vp, C.POINTER(Result), vp, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_cull": ([vp, C.POINTER(Result), vp, u32, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
+        "bvh_scene_cull": ([vp, vp, u32, u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_intersect_tris": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(BuildInput), u32, i32, vp, vp, u64, C.POINTER(u64)], i32),
         "bvh_closest_tris": ([vp, C.POINTER(Result), C.POINTER(BuildInput), C.POINTER(BuildInput), u32, C.c_float, vp, i32], i32),
         "bvh_intersect_all": ([vp, C.POINTER(Result), C.POINTER(BuildInput), vp, u32, u32, vp, vp, u64, C.POINTER(u64)], i32),
@@ -566,6 +570,75 @@ def cull(ctx, result, planes, path="auto", count_only: bool = False, capacity: i
                        capacity, "bvh_cull", own)
 
 
+def _as_volumes(planes):
+    """planes as f32 (n_volumes, planes_per_volume, 4); (planes_per_volume, 4) is one volume"""
+    pl = np.ascontiguousarray(planes, dtype=np.float32)
+    if pl.ndim == 2:
+        pl = pl[None]
+    if pl.ndim != 3 or pl.shape[2] != 4 or not 1 <= pl.shape[1] <= CULL_MAX_PLANES:
+        raise BvhError("planes must have shape (n_volumes, 1..8, 4) or (1..8, 4)")
+    return pl
+
+
+def scene_cull_object_planes(planes, object_to_world):
+    """bvh_scene_cull's object planes in numpy f32, every product and every sum a separate np.float32 operation: world planes (..., 4) under the forward
+    matrix ``object_to_world`` (..., 12) (row-major 3x4, m_rc = object_to_world[4r + c]), shapes broadcast:
+    a' = (a m00 + b m10) + c m20, b' and c' with columns 1 and 2, d' = ((a m03 + b m13) + c m23) + d.  Returns f32 (..., 4)."""
+    pl = np.asarray(planes, dtype=np.float32); m = np.asarray(object_to_world, dtype=np.float32)
+    a, b, c, d = pl[..., 0], pl[..., 1], pl[..., 2], pl[..., 3]
+    out = []
+    with np.errstate(invalid="ignore", over="ignore"):
+        for col in range(4):
+            x = a * m[..., col]; y = b * m[..., 4 + col]; z = c * m[..., 8 + col]
+            t = x + y
+            t = t + z
+            out.append((t + d) if col == 3 else t)
+    return np.stack(np.broadcast_arrays(*out), axis=-1).astype(np.float32)
+
+
+def scene_cull_brute_force(planes, blas_leaf_boxes, instances, world_boxes):
+    """bvh_scene_cull's defined answer by testing every leaf box of every active instance against every volume (the reference of the CPU and of the GPU
+    tests).  ``planes``: world-space floats (n_volumes, planes_per_volume, 4), or (planes_per_volume, 4) for one volume; ``blas_leaf_boxes``: per BLAS, AABB
+    records or (n, 6) floats indexed by primitive; ``instances``: INSTANCE records, ``blas`` == INVALID (or out of range) marking an inactive one;
+    ``world_boxes``: the scene's stored world box of every instance, AABB records or (n_instances, 6) floats.  Pair (k, j) passes volume i iff k is active,
+    k's world box passes cull_plane_values' p-vertex test against the world planes, and leaf box j of k's BLAS is valid and passes it against
+    scene_cull_object_planes(planes[i], object_to_world[k]); bit p of straddle is !(s'(n-vertex of object plane p) >= 0).  Returns (offsets
+    u32[n_volumes + 1], records SCENE_CULL_HIT[total]), every slice in ascending (instance, prim) order."""
+    pl = _as_volumes(planes)
+    nv, per = pl.shape[0], pl.shape[1]
+    wlo, whi = _box_corners(world_boxes)
+    inst = np.asarray(instances)
+    bits = (np.uint32(1) << np.arange(per, dtype=np.uint32))[None, :, None]
+    zero = np.float32(0.0)
+    parts = []                                            # (volume, instance, prim, straddle) arrays
+    for k in range(len(inst)):
+        bl = int(inst["blas"][k])
+        if bl >= len(blas_leaf_boxes):
+            continue
+        with np.errstate(invalid="ignore"):
+            s_w, _ = cull_plane_values(pl, wlo[k], whi[k])                               # (volumes, planes)
+            enter = bool((wlo[k] <= whi[k]).all()) & (s_w >= zero).all(axis=1)
+        vols = np.nonzero(enter)[0]
+        if len(vols) == 0:
+            continue
+        lo, hi = _box_corners(blas_leaf_boxes[bl])
+        obj = scene_cull_object_planes(pl[vols], inst["object_to_world"][k])              # (v, planes, 4)
+        s_p, s_n = cull_plane_values(obj[:, :, None, :], lo[None, None], hi[None, None])  # (v, planes, n)
+        with np.errstate(invalid="ignore"):
+            inside = (lo <= hi).all(axis=1)[None] & (s_p >= zero).all(axis=1)
+            mask = np.where(s_n >= zero, np.uint32(0), bits).sum(axis=1, dtype=np.uint32)
+        vi, pj = np.nonzero(inside)
+        parts.append((vols[vi], np.full(len(vi), k, dtype=np.int64), pj, mask[vi, pj]))
+    rec = np.zeros(sum(len(p[0]) for p in parts), dtype=SCENE_CULL_HIT)
+    offsets = np.zeros(nv + 1, dtype=np.uint64)
+    if len(rec):
+        v, k, j, msk = (np.concatenate([p[c] for p in parts]) for c in range(4))
+        order = np.lexsort((j, k, v))
+        rec["prim"], rec["instance"], rec["straddle"] = j[order], k[order], msk[order]
+        offsets[1:] = np.cumsum(np.bincount(v, minlength=nv))
+    return np.minimum(offsets, 0xFFFFFFFF).astype(np.uint32), rec
+
+
 def many_layout(counts):
     """bvh_build_many's output layout: (out_off, node_off, total) for the meshes' triangle counts — mesh m's d_prim_aabbs / d_sorted_* slices start at
     out_off[m] (the exclusive scan of the counts), its 2*count-1 node records at record node_off[m] = 2*out_off[m] - m; total = the sum of the counts."""
@@ -832,6 +905,13 @@ class Context:
 
     def synchronize(self) -> None:
         _check(lib().bvh_ctx_synchronize(self.handle), "bvh_ctx_synchronize")
+
+    def query_overflow(self) -> tuple[int, int]:
+        """bvh_ctx_query_overflow: how many queries the stack walks of the last query call's first (count) pass and of its fill pass left to the stackless
+        kernels (waits for the stream)"""
+        a, b = C.c_uint32(), C.c_uint32()
+        _check(lib().bvh_ctx_query_overflow(self.handle, C.byref(a), C.byref(b)), "bvh_ctx_query_overflow")
+        return a.value, b.value
 
     def upload(self, host: np.ndarray) -> DeviceBuffer:
         return DeviceBuffer(self, host.nbytes).upload(host)
@@ -2005,6 +2085,25 @@ class Scene:
         with np.errstate(invalid="ignore"):
             d = np.sqrt(hits["dist2"])
             return np.where(w > np.float32(0.5), -d, d).astype(np.float32), hits
+
+    def cull(self, planes, path="auto", count_only: bool = False, capacity: int | None = None):
+        """bvh_scene_cull: every (instance, triangle) pair whose leaf box passes each WORLD-space convex volume of ``planes``, the instance judged by its stored
+        world box and its leaves by the object planes of the volume under the instance's forward matrix.  ``planes`` and ``path`` as for the module's cull.
+        Returns host arrays (offsets u32[n_volumes + 1], records SCENE_CULL_HIT[total]): volume i's records are records[offsets[i]:offsets[i + 1]], in no
+        particular order; ``straddle == 0`` marks a leaf box wholly inside the volume.  ``count_only`` returns offsets alone.  ``capacity`` None: a
+        count-only call first, then a call with the exact capacity; a given capacity that is too small is re-allocated with the total the call reported
+        and the call repeated once."""
+        pl = _as_volumes(planes)
+        if path not in CULL_PATHS and path not in CULL_PATHS.values():
+            raise BvhError('path must be "auto", "lane" or "group"')
+        mode = CULL_PATHS.get(path, path)
+        n, per = pl.shape[0], pl.shape[1]
+        if n == 0:                                        # no volumes: the empty answer, without a call
+            return _no_queries(count_only, SCENE_CULL_HIT)
+        own = self.ctx.upload(pl)
+        self._sync_blas()
+        return _count_fill(self.ctx, lambda off, out, cap, tot: lib().bvh_scene_cull(self.handle, own.ptr, n, per, mode, off, out, cap, tot), n,
+                           SCENE_CULL_HIT, count_only, capacity, "bvh_scene_cull", own)
 
     def cull_instances(self, planes, path="auto", count_only: bool = False, capacity: int | None = None):
         """bvh_cull on this scene's top-level tree (tlas()): which instances' world boxes pass each convex volume of ``planes``; the records' ``prim`` is the

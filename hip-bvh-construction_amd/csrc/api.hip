@@ -539,7 +539,7 @@ int bvh_ctx_create_on_stream(int device, void* hip_stream, bvh_ctx** out) {
     // the build path's code objects are loaded here, once per process and device, not by a context's first build (first build of a fresh process at 262 144 triangles:
     // 2.4 ms against 0.13 warm; first HPLOC / PLOC++ build after that 0.51 / 0.65 against 0.18 / 0.38 — tools/cold_probe.py)
     { static std::once_flag warmed[64];
-      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_tris(); warm_scene_closest_tris(); warm_scene_radius_tris(); warm_scene_collide(); warm_scene_winding(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_closest_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_radius_tris(); warm_split(); warm_many(); warm_many_ploc(); }); }
+      std::call_once(warmed[device & 63], [] { warm_stage_em(); warm_sort(); warm_lbvh(); warm_hploc(); warm_ploc(); warm_misc(); warm_collapse(); warm_refit(); warm_refit_subset(); warm_query(); warm_optimize(); warm_scene(); warm_scene_point(); warm_scene_knn(); warm_scene_multihit(); warm_scene_radius(); warm_scene_overlap(); warm_scene_cull(); warm_scene_tris(); warm_scene_closest_tris(); warm_scene_radius_tris(); warm_scene_collide(); warm_scene_winding(); warm_point_query(); warm_winding(); warm_overlap(); warm_tris(); warm_closest_tris(); warm_knn(); warm_multihit(); warm_radius(); warm_radius_tris(); warm_split(); warm_many(); warm_many_ploc(); }); }
     *out = c;
     return 0;
 }
@@ -600,6 +600,18 @@ int bvh_ctx_set_kernel_filter(bvh_ctx* c, const char* kernel_name) {
 int bvh_ctx_set_kernel_sampling(bvh_ctx* c, uint32_t every) {
     if (!c || every == 0) return BVH_E_INVALID_ARG;
     c->sample_every = every; c->build_counter = 0; c->recorder.reset();
+    return 0;
+}
+// the two overflow words of the ctx's last query call, after its work is done: how many queries the stack walks of the (count) pass and of the fill pass left
+// to the stackless kernels.  Blocks on the stream and on an 8-byte read-back; for tests and diagnosis
+int bvh_ctx_query_overflow(bvh_ctx* c, uint32_t* first_pass_out, uint32_t* fill_pass_out) {
+    if (!c || !c->arena) return BVH_E_INVALID_ARG;
+    Bind b(c->device);
+    u32 w[2] = { 0, 0 };
+    HIP_TRY(hipMemcpyAsync(w, overflow_words(c), sizeof w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (first_pass_out) *first_pass_out = w[0];
+    if (fill_pass_out) *fill_pass_out = w[1];
     return 0;
 }
 int bvh_ctx_synchronize(bvh_ctx* c) { if (!c) return BVH_E_INVALID_ARG; Bind b(c->device); return herr(hipStreamSynchronize(c->stream)); }
@@ -1806,6 +1818,30 @@ int bvh_scene_overlap(bvh_scene* sc, const bvh_aabb* d_boxes, uint32_t n_boxes, 
         const SceneHits h{ d_offsets, d_prims, total, capacity };
         launch_scene_overlap_count(s, q, h, sc->ctx->overlap_sums, total);
         if (d_prims) { q.overflow = overflow + 1; launch_scene_overlap_fill(s, (flags & BVH_SCENE_OVERLAP_SORTED) ? 1 : 0, q, h); }
+    });
+}
+
+// bvh_cull's volumes on a scene, bvh_scene_overlap's tail; every argument is checked before anything is enqueued, so an error writes nothing.  The walk is chosen
+// here: BVH_CULL_AUTO takes the group walk for few volumes on a scene large enough to fill a workgroup's rounds (kernels.hpp's two constants)
+int bvh_scene_cull(bvh_scene* sc, const float* d_planes, uint32_t n_volumes, uint32_t planes_per_volume, int path, uint32_t* d_offsets,
+                   bvh_scene_cull_hit* d_hits, uint64_t capacity, uint64_t* total_out) {
+    if (!sc || !d_planes || !d_offsets || !sc->built) return BVH_E_INVALID_ARG;
+    if (planes_per_volume < 1u || planes_per_volume > (uint32_t)BVH_CULL_MAX_PLANES) return BVH_E_INVALID_ARG;
+    if (path != BVH_CULL_AUTO && path != BVH_CULL_LANE && path != BVH_CULL_GROUP) return BVH_E_INVALID_ARG;
+    if (n_volumes >= (1u << 30)) return BVH_E_INVALID_ARG;
+    const Range rs[3] = { Range(d_planes, (uint64_t)n_volumes * planes_per_volume * 4u * sizeof(float)), Range(d_offsets, ((uint64_t)n_volumes + 1u) * sizeof(u32)),
+                          fill_range(d_hits, capacity, sizeof(bvh_scene_cull_hit)) };
+    if (!disjoint(rs, 3, 3)) return BVH_E_INVALID_ARG;        // the three caller arrays must not overlap
+    uint32_t largest = 0;
+    for (uint32_t n : sc->blas_n) largest = n > largest ? n : largest;
+    const bool group = path == BVH_CULL_GROUP || (path == BVH_CULL_AUTO && n_volumes <= SCENE_CULL_AUTO_MAX_VOLUMES &&
+                                                  (uint64_t)sc->n_inst + largest >= SCENE_CULL_AUTO_MIN_LEAVES);
+    const uint64_t max_pops = (uint64_t)sc->n_inst * ((uint64_t)largest + 2u);      // (every instance's internal nodes and the top level's: a tree expands fewer)
+    return count_fill_tail(sc->ctx, nullptr, n_volumes, d_offsets, total_out, [&](hipStream_t s, u32* overflow, u64* total) {
+        SceneQuery q = scene_query(sc, d_planes, n_volumes, d_hits, overflow);
+        const SceneHits h{ d_offsets, d_hits, total, capacity };
+        launch_scene_cull_count(s, group, q, h, planes_per_volume, max_pops, sc->ctx->overlap_sums, total);
+        if (d_hits) { q.overflow = overflow + 1; launch_scene_cull_fill(s, group, q, h, planes_per_volume, max_pops); }
     });
 }
 

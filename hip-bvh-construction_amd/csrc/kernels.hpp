@@ -357,6 +357,16 @@ void launch_scene_radius_fill(hipStream_t s, int sorted, const SceneQuery& q, co
 // once unless *h.total <= h.capacity and *h.total < 2^32; query i's records go to hits[offsets[i] ..], in ascending (instance, prim) order when sorted != 0
 void launch_scene_overlap_count(hipStream_t s, const SceneQuery& q, const SceneHits& h, uint64_t* d_sums, uint64_t* d_total);
 void launch_scene_overlap_fill(hipStream_t s, int sorted, const SceneQuery& q, const SceneHits& h);
+// bvh_scene_cull (scene_cull.hip): the same two calls over convex volumes (q.rays = float[n_rays][planes][4], WORLD space), with hits =
+// bvh_scene_cull_hit[capacity].  group false: k_scene_cull_walk (one volume per lane, the short stack shared by both levels); group true: k_scene_cull_group (one
+// volume per workgroup of CULL_GROUP_BLOCK threads, LDS work stack of BVH_SCENE_CULL_GROUP_STACK {instance, node} entries; max_pops bounds its expansions on
+// arrays that are not a tree).  Either marks a volume it cannot finish and k_scene_cull_deep (stackless, returns at once while *q.overflow == 0) redoes it.
+// launch_scene_cull_count ends with launch_overlap_scan; launch_scene_cull_fill's kernels return at once unless *h.total <= h.capacity and *h.total < 2^32
+constexpr uint32_t SCENE_CULL_AUTO_MAX_VOLUMES = CULL_AUTO_MAX_VOLUMES;   // BVH_CULL_AUTO on a scene takes the group walk iff n_volumes <= this (bvh_cull's measured value) ...
+constexpr uint32_t SCENE_CULL_AUTO_MIN_LEAVES = 1024;                     // ... and n_instances + the largest BLAS's n_leaves >= this (carried over from bvh_cull: DESIGN.md §8zc)
+void launch_scene_cull_count(hipStream_t s, bool group, const SceneQuery& q, const SceneHits& h, uint32_t planes, uint64_t max_pops, uint64_t* d_sums,
+                             uint64_t* d_total);
+void launch_scene_cull_fill(hipStream_t s, bool group, const SceneQuery& q, const SceneHits& h, uint32_t planes, uint64_t max_pops);
 // bvh_scene_intersect_tris (scene_tris.hip): the same two calls over query triangles (q.rays is unused), with hits = bvh_instance_prim[capacity].  SceneTris is
 // the query side: the caller's world-space mesh (mode BVH_SCENE_TRIS_QUERY) or the instance whose world triangles ask (BVH_SCENE_TRIS_INSTANCE; queries unused).
 // k_scene_tris_count + k_scene_tris_deep + launch_overlap_scan; launch_scene_tris_fill: k_scene_tris_fill + k_scene_tris_deep, which return at once unless
@@ -428,6 +438,6 @@ void launch_bvh4_cost(hipStream_t s, const void* d_wide, uint32_t n_wide, const 
 void launch_checksum(hipStream_t s, const void* d_nodes, uint32_t n_nodes, const void* d_leaves /*may be null*/, uint32_t n_leaves, uint32_t root, uint64_t* d_out /*[1], zeroed inside*/);
 
 // one kernel of each translation unit of the build path is touched (hipFuncGetAttributes): the runtime loads that unit's code object now instead of at its first launch
-void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_tris(); void warm_scene_closest_tris(); void warm_scene_radius_tris(); void warm_scene_collide(); void warm_scene_winding(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_closest_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_radius_tris(); void warm_split(); void warm_many(); void warm_many_ploc();
+void warm_stage_em(); void warm_sort(); void warm_lbvh(); void warm_hploc(); void warm_ploc(); void warm_misc(); void warm_collapse(); void warm_refit(); void warm_refit_subset(); void warm_query(); void warm_optimize(); void warm_scene(); void warm_scene_point(); void warm_scene_knn(); void warm_scene_multihit(); void warm_scene_radius(); void warm_scene_overlap(); void warm_scene_cull(); void warm_scene_tris(); void warm_scene_closest_tris(); void warm_scene_radius_tris(); void warm_scene_collide(); void warm_scene_winding(); void warm_point_query(); void warm_winding(); void warm_overlap(); void warm_tris(); void warm_closest_tris(); void warm_knn(); void warm_multihit(); void warm_radius(); void warm_radius_tris(); void warm_split(); void warm_many(); void warm_many_ploc();
 
 } // namespace bvh

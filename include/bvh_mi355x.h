@@ -1251,6 +1251,42 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  *     vertex or index array.
  *   n_queries == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
  *   bvh_ctx_kernel_times reports k_scene_radius_tris_walk (count and fill), k_scene_radius_tris_deep (after each pass) and k_overlap_scan.
+ * Convex volumes: bvh_scene_cull is bvh_cull on a scene — which triangles' leaf boxes of which active instances pass each WORLD-space convex volume (a view
+ * frustum, the tile frusta of a view, shadow cascades against thousands of placed bodies), without flattening the scene and after bvh_scene_update alone.  It
+ * answers both phases in one call and tighter than bvh_cull on bvh_scene_tlas followed by a flat test: a plane maps to a plane under an affine map, so each
+ * instance is tested as its oriented box, not as the world box around it (tests/test_scene_cull.py restates the contract in numpy).
+ *   planes, volumes, p-vertex, n-vertex, s(v), "passes", straddle: bvh_cull's, word for word; d_planes is in WORLD space.
+ *   object planes of world plane (a, b, c, d) of volume i in instance k, with m_rc = object_to_world[4r + c] — the caller's forward matrix; no inverse is used:
+ *     a' = fadd(fadd(fmul(a, m00), fmul(b, m10)), fmul(c, m20)), b' and c' the same with columns 1 and 2,
+ *     d' = fadd(fadd(fadd(fmul(a, m03), fmul(b, m13)), fmul(c, m23)), d), each fmul / fadd ONE round-to-nearest f32 operation, never an FMA.  In exact
+ *     arithmetic a'x + b'y + c'z + d' is the world plane evaluated at M x + t.
+ *   test: pair (instance k, primitive j) passes volume i iff (1) instance k is active, (2) the scene's stored world box of k passes bvh_cull's test against
+ *     the WORLD planes — exactly what bvh_cull on bvh_scene_tlas tests —, (3) primitive j's leaf box, as bvh_overlap defines it in both layouts, is valid, and
+ *     (4) that leaf box passes bvh_cull's p-vertex test against the OBJECT planes of (i, k).  straddle bit p = !(s'(n-vertex of object plane p) >= 0), from
+ *     the leaf's own object box against all planes; zero is written 0.
+ *   answer: compressed rows as bvh_cull's, d_offsets[0] = 0, d_offsets[n_volumes] = the total; each pair appears at most once per slice; the order inside a
+ *     slice is unspecified, but the same call on the same arrays with the same path gives the same bytes (slots never come from atomics).
+ *   exactness: inside an instance the object planes are fixed numbers, so bvh_cull's argument (monotone products and sums) holds verbatim below the BLAS
+ *     root, and top-level containment is bitwise, as before: every box above a passing leaf passes.  The set is exact for EVERY volume and independent of
+ *     builders, layouts and path whenever every BLAS's boxes nest (true of every tree the library makes) and no s or s' is a NaN.  Outside that condition
+ *     every reported pair still passes its own test and the slice is a subset.  The BLAS root's own box and the top-level root's own box are not tested, as
+ *     in bvh_scene_overlap (the world box stands for the former).  A one-instance scene has no top-level tree: its world box is tested, then the instance is
+ *     entered.
+ *   relations: one identity instance gives bvh_cull's {prim, straddle} set on the BLAS for every volume with finite planes (((a 1 + b 0) + c 0) == a as a
+ *     value; a zero's sign does not change n.k >= 0).  The instances occurring in slice i are a subset of slice i of bvh_cull on bvh_scene_tlas.  A slice
+ *     never contains an inactive instance.
+ *   path: bvh_cull_path.  BVH_CULL_LANE walks one volume per lane on both levels; BVH_CULL_GROUP gives each volume a workgroup of 256 threads and a work stack
+ *     of BVH_SCENE_CULL_GROUP_STACK {instance, node} entries in LDS, on bvh_cull's fixed schedule (each round the m = min(top, 256) entries at the top, thread
+ *     t entry top - m + t; a passing top-level leaf whose instance is active is pushed as that BLAS's root; emits and pushes in thread order, left before
+ *     right); BVH_CULL_AUTO takes the group walk iff n_volumes <= 65536 and n_instances + the largest registered BLAS's n_leaves >= 1024.
+ *   passes, capacity, total_out, saturation, BVH_E_TOO_LARGE, asynchrony, scratch words: exactly bvh_scene_overlap's — the call always counts and scans; the
+ *     fill decides ON THE DEVICE whether it runs (d_hits != NULL, total <= capacity, total < 2^32) and otherwise leaves d_hits untouched with d_offsets
+ *     complete; the 8-byte read-back happens only with total_out != NULL; a volume's counter saturates at 0xFFFFFFFD.  No depth or size limit at either
+ *     level: a volume whose short stack or work stack would overflow is finished by a stackless pass through the top-level plan and the BLAS plans.
+ *   errors (nothing is written or enqueued, BVH_E_INVALID_ARG): NULL or unbuilt scene, NULL d_planes or d_offsets, planes_per_volume outside 1 .. 8, path
+ *     outside 0 .. 2, n_volumes >= 2^30, d_offsets or d_hits (capacity records) overlapping d_planes or each other.
+ *   n_volumes == 0: returns 0, writes d_offsets[0] = 0 and *total_out = 0, touches nothing else.  BLAS ordering as for bvh_scene_intersect.
+ *   bvh_ctx_kernel_times reports k_scene_cull_walk or k_scene_cull_group (count and fill), k_scene_cull_deep (after each pass) and k_overlap_scan.
  * Winding numbers: bvh_scene_winding_number is bvh_winding_number on a scene — inside / outside against an assembly of bodies, the sign for
  * bvh_scene_closest_point's distance, voxelisation and point-in-union over thousands of bvh_build_many bodies — without flattening the scene.  Two calls:
  * bvh_scene_winding_prepare after a build or an update, bvh_scene_winding_number per batch of points (tests/test_scene_winding.py restates both in numpy).
@@ -1320,6 +1356,12 @@ int  bvh_scene_radius_search(bvh_scene* scene, const bvh_point_query* d_points, 
 int  bvh_scene_overlap(bvh_scene* scene, const bvh_aabb* d_boxes, uint32_t n_boxes, uint32_t flags /* 0 or BVH_SCENE_OVERLAP_SORTED */,
                        uint32_t* d_offsets /* u32[n_boxes + 1], device */, bvh_instance_prim* d_prims /* [capacity], device, or NULL: count only */,
                        uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
+typedef struct { uint32_t prim; uint32_t instance; uint32_t straddle; uint32_t zero; } bvh_scene_cull_hit;   /* 16 bytes, one store */
+#define BVH_SCENE_CULL_GROUP_STACK 8192   /* entries {instance, node} of the group walk's LDS work stack: 64 KiB, two workgroups per CU */
+int  bvh_scene_cull(bvh_scene* scene, const float* d_planes /* float[n_volumes][planes_per_volume][4], device, WORLD space */,
+                    uint32_t n_volumes, uint32_t planes_per_volume /* 1 .. BVH_CULL_MAX_PLANES */, int path /* bvh_cull_path */,
+                    uint32_t* d_offsets /* u32[n_volumes + 1], device */, bvh_scene_cull_hit* d_hits /* [capacity], device, or NULL: count only */,
+                    uint64_t capacity, uint64_t* total_out /* host, may be NULL */);
 typedef enum { BVH_SCENE_TRIS_QUERY = 0, BVH_SCENE_TRIS_INSTANCE = 1 } bvh_scene_tris_mode;
 #define BVH_SCENE_TRIS_SORTED 1u
 int  bvh_scene_intersect_tris(bvh_scene* scene, const bvh_build_input* queries /* world-space mesh, device, any bvh_tri_format; NULL with BVH_SCENE_TRIS_INSTANCE */,
@@ -1461,6 +1503,10 @@ void bvh_batch_destroy(bvh_batch* batch);
  * has landed — the host polls it, which notices the end of the build a few microseconds before hipStreamSynchronize does —
  * i.e. when every launch of the build has completed) */
 int  bvh_ctx_synchronize(bvh_ctx* ctx);
+/* the overflow words of the ctx's last query call (a scene's calls use its ctx's): how many queries the stack walks of its first (count) pass and of its fill
+ * pass left to the stackless kernels; either pointer may be NULL.  Waits for the stream and reads 8 bytes back: for tests and diagnosis.  BVH_E_INVALID_ARG for
+ * a NULL ctx or one that has never reserved its arena */
+int  bvh_ctx_query_overflow(bvh_ctx* ctx, uint32_t* first_pass_out, uint32_t* fill_pass_out);
 
 /* plain device-memory helpers so that hosts without a HIP binding (ctypes, cgo, JNI ...) can stage buffers */
 int  bvh_dev_alloc(bvh_ctx* ctx, uint64_t bytes, void** out);

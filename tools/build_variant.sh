@@ -32,6 +32,7 @@ for f in hploc ploc; do /opt/rocm/bin/hipcc $FLAGS -fno-honor-nans -mno-amdgpu-i
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c radius_tris.hip -o $OBJ/radius_tris.o &     # (as the Makefile)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene_radius_tris.hip -o $OBJ/scene_radius_tris.o &     # (as the Makefile)
 /opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c cull.hip -o $OBJ/cull.o &     # (as the Makefile)
+/opt/rocm/bin/hipcc $FLAGS -fno-slp-vectorize $EXTRA -c scene_cull.hip -o $OBJ/scene_cull.o &     # (as the Makefile)
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJ/*.o -L/opt/rocm/lib -lrccl -o $OUT/libbvh_$NAME.so
 echo built $OUT/libbvh_$NAME.so
