@@ -501,14 +501,15 @@ def _box_corners(leaf_boxes):
 
 def cull_plane_values(planes, lo, hi):
     """bvh_cull's plane test in numpy f32, every product and every sum a separate np.float32 operation: planes (..., 4) against boxes lo / hi (..., 3), shapes
-    broadcast.  Returns (s_p, s_n): s at the p-vertex (p.k = hi.k where n.k >= 0, else lo.k) and at the n-vertex (the other choice)."""
+    broadcast.  A product whose plane coefficient is +-0 contributes +0.0 whatever the coordinate (never 0 * inf = NaN).  Returns (s_p, s_n): s at the p-vertex
+    (p.k = hi.k where n.k >= 0, else lo.k) and at the n-vertex (the other choice)."""
     pl = np.asarray(planes, dtype=np.float32); lo = np.asarray(lo, dtype=np.float32); hi = np.asarray(hi, dtype=np.float32)
-    d = pl[..., 3]
+    d = pl[..., 3]; zero = np.float32(0.0)
     with np.errstate(invalid="ignore", over="ignore"):
-        sel = [pl[..., k] >= np.float32(0.0) for k in range(3)]
+        sel = [pl[..., k] >= zero for k in range(3)]
 
         def s_of(v):
-            x = pl[..., 0] * v[0]; y = pl[..., 1] * v[1]; z = pl[..., 2] * v[2]
+            x, y, z = (np.where(pl[..., k] == zero, zero, pl[..., k] * v[k]) for k in range(3))
             t = x + y
             t = t + z
             return (t + d).astype(np.float32)

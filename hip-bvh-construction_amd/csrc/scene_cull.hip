@@ -47,6 +47,7 @@ __device__ __forceinline__ Planes scull_object_planes(const Planes& W, u32 np, c
         O.c[k] = on ? __fadd_rn(__fadd_rn(__fmul_rn(a, M.r0.z), __fmul_rn(b, M.r1.z)), __fmul_rn(c, M.r2.z)) : 0.0f;
         O.d[k] = on ? __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a, M.r0.w), __fmul_rn(b, M.r1.w)), __fmul_rn(c, M.r2.w)), d) : 1.0f;
     }
+    planes_pick(O);
     return O;
 }
 

@@ -554,8 +554,11 @@ int  bvh_overlap(bvh_ctx* ctx, const bvh_result* tree, const bvh_aabb* d_boxes, 
  * intersection of its planes_per_volume (1 .. BVH_CULL_MAX_PLANES) half-spaces; a caller with fewer real planes pads with (0, 0, 0, 1).
  * The test, for a plane with n = (a, b, c) and a box [lo, hi] with lo.k <= hi.k on every axis (bvh_overlap's validity test), in IEEE f32:
  *   p-vertex: p.k = (n.k >= 0) ? hi.k : lo.k (so -0.0 selects hi); the n-vertex takes the other choice on every axis;
- *   s(v) = fadd(fadd(fadd(fmul(a, v.x), fmul(b, v.y)), fmul(c, v.z)), d), every product and sum ONE round-to-nearest f32 operation (never an FMA);
- *   the box passes the plane iff s(p) >= 0 — a NaN fails —, and passes the volume iff it passes every plane;
+ *   s(v) = fadd(fadd(fadd(t(a, v.x), t(b, v.y)), t(c, v.z)), d), every product and sum ONE round-to-nearest f32 operation (never an FMA), with
+ *   t(coef, x) = fmul(coef, x) for a coefficient that is not zero and a zero for a coefficient of +0 or -0, WHATEVER x is (never 0 * inf = NaN; the sign of
+ *   that zero is not specified and cannot change an `s >= 0`): the padding plane and axis-aligned planes are immune to box planes at +-inf;
+ *   the box passes the plane iff s(p) >= 0 — a NaN fails —, and passes the volume iff it passes every plane.  A NaN comes only from inf - inf between terms
+ *   whose coefficients are not zero (a product that overflows against an infinite d, a box with infinite planes on two axes), or from a NaN in the input;
  *   bit k of straddle = !(s(n-vertex of plane k) >= 0): the box is not wholly inside plane k.  straddle == 0: the box lies wholly inside the volume (a
  *   renderer then skips clipping).  An invalid box (inverted, or with a NaN) passes nothing.
  * This is the standard conservative box test: a box beyond a corner or an edge of the volume can pass every plane without touching the volume.  That is the
@@ -565,7 +568,8 @@ int  bvh_overlap(bvh_ctx* ctx, const bvh_result* tree, const bvh_aabb* d_boxes, 
  * Each primitive appears at most once per slice.  The order inside a slice is unspecified, but the same call on the same arrays with the same path gives the
  * same bytes.
  * Exactness condition: every internal box contains its children's boxes — true bitwise of every tree this library makes —, and no evaluation of s produces a
- * NaN — true of finite boxes and planes whose products and sums do not overflow.  The test is monotone under containment in rounded f32 (products by a fixed
+ * NaN — true of finite planes whose products and sums do not overflow, on finite boxes and, for the terms with a zero coefficient, on boxes with infinite
+ * planes as well (a mesh with one vertex at +inf is answered exactly by every volume of axis-aligned or padded planes).  The test is monotone under containment in rounded f32 (products by a fixed
  * factor and sums are monotone, and the p-vertex takes the larger coordinate of every product), so every box above a passing leaf passes: the set is exact for
  * EVERY volume and does not depend on the builder, the layout or the path.  Outside that condition every reported primitive still passes its own leaf test,
  * but some may be left out.  A walk may drop plane k below a node whose n-vertex has s >= 0 (s(n_parent) <= s(n_child) <= s(p_child)): result-preserving under
@@ -1255,7 +1259,10 @@ int  bvh_optimize(bvh_ctx* ctx, bvh_result* io, uint32_t rounds, bvh_timings* ti
  * frustum, the tile frusta of a view, shadow cascades against thousands of placed bodies), without flattening the scene and after bvh_scene_update alone.  It
  * answers both phases in one call and tighter than bvh_cull on bvh_scene_tlas followed by a flat test: a plane maps to a plane under an affine map, so each
  * instance is tested as its oriented box, not as the world box around it (tests/test_scene_cull.py restates the contract in numpy).
- *   planes, volumes, p-vertex, n-vertex, s(v), "passes", straddle: bvh_cull's, word for word; d_planes is in WORLD space.
+ *   planes, volumes, p-vertex, n-vertex, s(v) with its rule for zero coefficients, "passes", straddle: bvh_cull's, word for word; d_planes is in WORLD space.
+ *     The rule applies to the numbers each test multiplies: the world coefficients against the world boxes, the OBJECT coefficients a', b', c' below against
+ *     the leaf boxes (the object planes themselves are plain products and sums: an infinite matrix entry times a zero coefficient is still a NaN).  A NaN
+ *     s or s' then comes only from inf - inf between terms whose coefficients are not zero, or from a NaN in the input.
  *   object planes of world plane (a, b, c, d) of volume i in instance k, with m_rc = object_to_world[4r + c] — the caller's forward matrix; no inverse is used:
  *     a' = fadd(fadd(fmul(a, m00), fmul(b, m10)), fmul(c, m20)), b' and c' the same with columns 1 and 2,
  *     d' = fadd(fadd(fadd(fmul(a, m03), fmul(b, m13)), fmul(c, m23)), d), each fmul / fadd ONE round-to-nearest f32 operation, never an FMA.  In exact

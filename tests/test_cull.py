@@ -317,14 +317,15 @@ def test_exact_boundaries(pkg):
                                       [(1.0, 0.0, 0.0, -np.nextafter(box[0, 0], F32(np.inf)))]], box)
     assert off.tolist() == [0, 1, 1, 2, 3]                           # through the max face: s(p) = 0 passes; one ulp beyond: fails
     assert hits["straddle"].tolist() == [1, 0, 1]                    # through the min face: s(n) = 0, wholly inside; one ulp beyond: straddles
-    # n.k = -0.0 selects hi for the p-vertex (-0.0 >= 0): with hi.x = +inf the product is a NaN and the box fails, while the n-vertex (lo.x) gives s = d
+    # n.k = -0.0 selects hi for the p-vertex (-0.0 >= 0): with hi.x = +inf the product would be a NaN, but a +-0 coefficient contributes +0 whatever the
+    # coordinate: s = d at both vertices, and the box passes wholly inside
     inf_box = np.array([[0.0, 0.0, 0.0, np.inf, 1.0, 1.0]], dtype=F32)
     s_p, s_n = pkg.cull_plane_values(np.array([-0.0, 0.0, 0.0, 1.0], dtype=F32), inf_box[0, :3], inf_box[0, 3:])
-    assert np.isnan(s_p) and s_n == 1.0
+    assert s_p == 1.0 and s_n == 1.0
     s_p, s_n = pkg.cull_plane_values(np.array([0.0, 0.0, 0.0, 1.0], dtype=F32), inf_box[0, :3], inf_box[0, 3:])
-    assert np.isnan(s_p) and s_n == 1.0
+    assert s_p == 1.0 and s_n == 1.0
     off, hits = pkg.cull_brute_force([[(-0.0, 0.0, 0.0, 1.0)]], inf_box)
-    assert off.tolist() == [0, 0]
+    assert off.tolist() == [0, 1] and hits["straddle"].tolist() == [0]
     # a NaN in a plane, an inverted box and a box with a NaN pass nothing; the padding plane passes every finite box with its bit clear
     bad = np.array([[0, 0, 0, 1, 1, 1], [1, 0, 0, 0, 1, 1], [0, np.nan, 0, 1, 1, 1]], dtype=F32)
     off, hits = pkg.cull_brute_force([[PADDING], [(0.0, 0.0, np.nan, 1.0)], [(np.nan, 0.0, 0.0, 1.0)]], bad)
